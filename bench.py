@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path's headline benchmark (BASELINE.json).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already
 resident in HBM.  At N=1 the workload is BASELINE.json configs[1]: p256r1 variable-base
@@ -434,6 +434,24 @@ def cpu_baseline(ora, curve, op, args, n, ks, ks2, pts):
                                      "would be benches/curves.rs:247-265)"}
 
 
+# --dump-outputs: units written per array.  2^16 rows of the widest output (p521r1, 132 bytes) as float32 come to
+# 35 MB, under the 64 MB the dump may take; float32 holds every byte value exactly.
+DUMP_ROWS = 1 << 16
+
+
+def dump_outputs(path, out, flags):
+    """The rows of a fixed seeded sample of the batch, in unit order: out (rows x bytes per result) and flags
+    (rows), as float32 .npy files under `path`."""
+    import numpy as np
+    import torch
+
+    rows = out.shape[0]
+    idx = torch.randperm(rows, generator=torch.Generator().manual_seed(2))[:DUMP_ROWS].sort().values.to(out.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "points.npy"), out[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "flags.npy"), flags[idx].cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -443,6 +461,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-path", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
     ap.add_argument("--cpu-sample", type=int, default=1 << 17)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/points.npy (the output bytes, one row per unit) "
+                         "and DIR/flags.npy, float32, for a fixed seeded sample of 2^16 units")
     ap.add_argument("--variant", default="default", choices=["default", "mirror", "lds", "l2", "ct", "ctg", "ctsub", "glv", "xonly"],
                     help="default: fast kernels; mirror: reference-mirroring kernels; "
                          "lds: ed25519 fixed base with a signed 6-bit comb table resident in LDS; "
@@ -451,6 +472,8 @@ def main():
                          "ctsub: ECCX_CT_SCAN | ECCX_ASSUME_SUBGROUP (bls12_381_g1, bases in G1); "
                          "glv: ECCX_ASSUME_SUBGROUP (bls12_381_g1 endomorphism ladder)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # ECCX_FORCE_DIST=1: initialise RCCL and run the gather pipeline even at world size 1, so that a
     # one-GPU box exercises process-group init, the asynchronous gather on RCCL's stream and its
     # ordering against the engine's kernels
@@ -628,6 +651,8 @@ def main():
                                 pts[idx].cpu().numpy().tobytes() if pts is not None else None)
         parity = (g_out[idx].cpu().numpy().tobytes() == w_out) and (g_flags[idx].cpu().numpy().tobytes() == w_inf)
         parity = parity and (out[idx].cpu().numpy().tobytes() == w_out)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, g_out, g_flags)
         if world > 1:
             peer = world - 1
             sel = idx_cpu.numpy()

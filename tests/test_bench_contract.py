@@ -4,6 +4,8 @@ multiplier-count model is self-consistent.  CPU only."""
 import importlib.util
 import json
 import os
+import subprocess
+import sys
 
 import pytest
 
@@ -108,6 +110,31 @@ def test_multiplier_model():
     assert m < g
     glv = bench.VARIANT_MULT[("bls12_381_g1_var_2^20", "glv")]["mad"]
     assert glv < 0.7 * bench.WORKLOADS["bls12_381_g1_var_2^20"][4]["mad"]
+
+
+def test_dump_outputs_is_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs writes the same seeded sample of rows every time, every byte exact in float32, within 64 MB at the
+    widest output (p521r1 affine points: 132 bytes per unit)."""
+    import numpy as np
+    import torch
+
+    n, cols = 1 << 19, 132
+    out = torch.randint(0, 256, (n, cols), dtype=torch.uint8, generator=torch.Generator().manual_seed(5))
+    flags = torch.randint(0, 3, (n,), dtype=torch.uint8, generator=torch.Generator().manual_seed(6))
+    bench.dump_outputs(str(tmp_path / "a"), out, flags)
+    bench.dump_outputs(str(tmp_path / "b"), out, flags)
+    pts, fl = np.load(tmp_path / "a" / "points.npy"), np.load(tmp_path / "a" / "flags.npy")
+    assert pts.dtype == fl.dtype == np.float32 and pts.shape == (bench.DUMP_ROWS, cols) and fl.shape == (bench.DUMP_ROWS,)
+    assert (pts == np.load(tmp_path / "b" / "points.npy")).all() and (fl == np.load(tmp_path / "b" / "flags.npy")).all()
+    sel = torch.randperm(n, generator=torch.Generator().manual_seed(2))[:bench.DUMP_ROWS].sort().values
+    assert (pts.astype(np.uint8) == out[sel].numpy()).all() and (fl.astype(np.uint8) == flags[sel].numpy()).all()
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("points.npy", "flags.npy")) <= 64 << 20
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 2 and "--steps" in r.stderr
 
 
 def test_usable_cores_is_sane():

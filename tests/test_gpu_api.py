@@ -4,6 +4,7 @@ points over two contexts, and the RCCL gather path on one GPU (ECCX_FORCE_DIST).
 compared with the oracle bit for bit.
 """
 import ctypes
+import importlib.util
 import json
 import os
 import subprocess
@@ -219,6 +220,30 @@ def test_bench_with_forced_rccl_gather():
     assert line["parity_sample_ok"] is True
     assert "forced" in line["config"]["gather"]
     assert line["value"] > 1e7
+
+
+def test_bench_dump_outputs(oracle, tmp_path):
+    """--dump-outputs: the sampled rows of the last timed step as float32, the bytes the oracle computes for the same
+    seeded inputs; --steps is the number of timed steps and ms_per_step their mean."""
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "0", "--no-cpu-baseline",
+                        "--no-host-path", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["parity_sample_ok"] is True
+    curve, n = "p256r1", 1 << 20
+    pts, flags = np.load(tmp_path / "points.npy"), np.load(tmp_path / "flags.npy")
+    assert pts.dtype == flags.dtype == np.float32 and pts.shape == (bench.DUMP_ROWS, 64) and flags.shape == (bench.DUMP_ROWS,)
+    # the bench's inputs (seeds 10 and 1000 at rank 0), at the first 256 sampled units
+    sel = torch.randperm(n, generator=torch.Generator().manual_seed(2))[:bench.DUMP_ROWS].sort().values.numpy()[:256]
+    ks = W.random_scalars(curve, n, seed=10)[sel].tobytes()
+    bases = oracle.base(curve, W.random_scalars(curve, n, seed=1000)[sel].tobytes(), threads=16)[0]
+    w_out, w_inf, _ = oracle.var(curve, ks, bases, threads=16)
+    assert pts[:256].astype(np.uint8).tobytes() == w_out and flags[:256].astype(np.uint8).tobytes() == w_inf
 
 
 def test_gather_pipeline_on_rccl_world_of_one(oracle):
