@@ -21,7 +21,7 @@ namespace {
 
 using eccx::CurveOps;
 
-constexpr int NCURVES = 5;
+constexpr int NCURVES = 6;
 // internal kernel option bits (kernels.hpp)
 constexpr uint32_t K_BASE_IS_GENERATOR = 1u << 0;
 constexpr uint32_t K_OUT_TABLE = 1u << 1;
@@ -38,6 +38,7 @@ const CurveOps* ops_of(int curve) {
     case ECCX_P521R1: return &eccx::ops_P521();
     case ECCX_BLS12_381_G1: return &eccx::ops_BLS12_381();
     case ECCX_ED25519: return &eccx::ops_ED25519();
+    case ECCX_P256K1: return &eccx::ops_P256K1();
     default: return nullptr;
   }
 }
@@ -49,11 +50,11 @@ struct eccx_ctx {
   int cus = 0;
   hipStream_t stream = nullptr;
   hipStream_t in_stream = nullptr, out_stream = nullptr;  // host-buffer entry points: copies beside the compute
-  uint32_t* comb[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  uint32_t* comb_u[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // unsaturated-field copies
-  uint32_t* comb_lds[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // images for the LDS variant
-  uint32_t* comb_ct[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // signed-window tables of the secret-scalar path
-  uint32_t* comb_ctg[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ... of its lane-gather form (ECCX_CT_GATHER)
+  uint32_t* comb[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint32_t* comb_u[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // unsaturated-field copies
+  uint32_t* comb_lds[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // images for the LDS variant
+  uint32_t* comb_ct[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // signed-window tables of the secret-scalar path
+  uint32_t* comb_ctg[NCURVES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // ... of its lane-gather form (ECCX_CT_GATHER)
   std::mutex comb_mu;
   uint32_t* scratch = nullptr;
   size_t scratch_words = 0;
@@ -200,9 +201,10 @@ int launch_var(eccx_ctx* ctx, const CurveOps* ops, size_t n, const uint8_t* d_sc
   const bool fast = !mirror && ops->var_fast && !d_proj && !(kopts & K_OUT_TABLE);
   if (fast && ops->var_coz && d_points && !(kopts & K_BASE_IS_GENERATOR)) {
     // Weierstrass curves: the ladder over an affine window table (kernels_coz.hpp); glv: bases known to be in the
-    // prime-order subgroup.  Units with a base point of order <= 16 come back marked and are redone
-    // by the generic ladder, which otherwise only reads the flags.
-    const int g = glv ? 1 : 0;
+    // prime-order subgroup, or a curve whose endomorphism applies to every point (p256k1: var_glv_default).  Units
+    // with a base point of order <= 16 come back marked and are redone by the generic ladder, which otherwise only
+    // reads the flags.
+    const int g = (glv || ops->var_glv_default) ? 1 : 0;
     const int grid = ops->var_coz_grid(ctx->cus, n, g);
     const int grid2 = ops->var_fast_grid ? ops->var_fast_grid(ctx->cus, n) : grid_for(ctx, n);
     int rc = ensure_scratch(ctx, ops->coz_row_words, grid);

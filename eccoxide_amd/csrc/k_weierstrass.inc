@@ -117,8 +117,10 @@ hipError_t var_ct_(int grid, hipStream_t s, size_t n, const uint8_t* scalars, co
 #define ECCX_CT_GLV 1
 #endif
 using CtPrimeBases = std::conditional<ECCX_CURVE::PRIME_ORDER != 0, NoGlv, PrimeOrderBases>::type;
+// (a curve of prime order has no such kernel: var_ct_prime is null there and the plain form is instantiated for the grid query)
+constexpr bool CT_PRIME_GLV = COZ_HAS_GLV && ECCX_CT_GLV && ECCX_CURVE::PRIME_ORDER == 0;
 #define CT_PRIME_KERNEL \
-  (k_scalarmul_coz_unsat<ECCX_CURVE_U, std::conditional<(COZ_HAS_GLV && ECCX_CT_GLV), CozGlv, CtPrimeBases>::type, (COZ_HAS_GLV && ECCX_CT_GLV), false, \
+  (k_scalarmul_coz_unsat<ECCX_CURVE_U, std::conditional<CT_PRIME_GLV, CozGlv, CtPrimeBases>::type, CT_PRIME_GLV, false, \
                          ECCX_CT_VAR_BITS, true>)
 hipError_t var_ct_prime_(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* points, uint32_t* rows,
                          uint8_t* flags, uint32_t* scratch, uint32_t opts) {

@@ -107,6 +107,128 @@ ECCX_DEV void glv_split(uint32_t (&k1)[5], uint32_t (&k2)[5], const uint8_t* __r
   for (int i = 0; i < 5; ++i) { k1[i] = r[i]; k2[i] = q[i]; }
 }
 
+// ---- signed lattice split k = k1 + k2 lambda (secp256k1) -------------------------------------------
+// G::LATTICE: the endomorphism is [lambda] on every curve point and the split rounds against a reduced basis
+// (a1, b1), (a2, b2) of {(x, y): x + y lambda = 0 mod n}:
+//   k      mod n by one conditional subtraction (k < 2^256 < 2 n)
+//   c1     round(k g1 / 2^384), g1 = round(2^384 b2 / n);  c2 = round(k g2 / 2^384), g2 = round(-2^384 b1 / n)
+//   k1     k - c1 a1 - c2 a2;  k2 = -c1 b1 - c2 b2  (b1 < 0: + c1 |b1|)
+// Both halves lie in (-2^128, 2^128), so they are computed modulo 2^160 in two's complement.  Out: the magnitudes as
+// five little-endian words and the signs (1: negative).  Model: tests/p256k1_ref.py glv_split_lattice.
+template <class G>
+struct GlvLattice {
+  template <class T>
+  static constexpr bool has(decltype(T::LATTICE)*) { return T::LATTICE; }
+  template <class T>
+  static constexpr bool has(...) { return false; }
+  static constexpr bool value = has<G>(nullptr);
+};
+
+// r[0..4] = (a * b) mod 2^160 for a of 4 words and b of 5 words
+ECCX_DEV void glv_mul_lo160(uint32_t (&r)[5], const uint32_t (&a)[4], const uint32_t (&b)[5]) {
+#pragma unroll
+  for (int i = 0; i < 5; ++i) r[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; i + j < 5; ++j) {
+      const uint64_t t = (uint64_t)a[i] * b[j] + r[i + j] + carry;
+      r[i + j] = (uint32_t)t;
+      carry = t >> 32;
+    }
+  }
+}
+
+// c = round(k g / 2^384) for k, g of 8 words (c < 2^128 for k < n)
+template <class G>
+ECCX_DEV void glv_round384(uint32_t (&c)[4], const uint32_t (&k)[8], const uint32_t (&g)[8]) {
+  uint32_t prod[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) prod[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint64_t t = (uint64_t)k[i] * g[j] + prod[i + j] + carry;
+      prod[i + j] = (uint32_t)t;
+      carry = t >> 32;
+    }
+    prod[i + 8] = (uint32_t)carry;
+  }
+  uint32_t inc = prod[11] >> 31;  // bit 383: round half up
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint64_t t = (uint64_t)prod[12 + i] + inc;
+    c[i] = (uint32_t)t;
+    inc = (uint32_t)(t >> 32);
+  }
+}
+
+template <class G>
+ECCX_DEV void glv_split_lattice(uint32_t (&k1)[5], uint32_t (&k2)[5], uint32_t& s1, uint32_t& s2,
+                                const uint8_t* __restrict__ kb) {
+  uint32_t k[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint8_t* b = kb + 28 - 4 * i;
+    k[i] = ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | (uint32_t)b[3];
+  }
+  {  // k mod n
+    uint32_t d[8];
+    uint64_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint64_t t = (uint64_t)k[i] - G::N[i] - borrow;
+      d[i] = (uint32_t)t;
+      borrow = (t >> 32) & 1u;
+    }
+    const bool ge = borrow == 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = ge ? d[i] : k[i];
+  }
+  uint32_t c1[4], c2[4];
+  glv_round384<G>(c1, k, G::G1);
+  glv_round384<G>(c2, k, G::G2);
+  uint32_t t1[5], t2[5], t3[5], t4[5];
+  glv_mul_lo160(t1, c1, G::A1);
+  glv_mul_lo160(t2, c2, G::A2);
+  glv_mul_lo160(t3, c1, G::B1N);
+  glv_mul_lo160(t4, c2, G::B2);
+  // h1 = k - t1 - t2, h2 = t3 - t4 (mod 2^160)
+  uint32_t h1[5], h2[5];
+  {
+    int64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      c += (int64_t)k[i] - (int64_t)t1[i] - (int64_t)t2[i];
+      h1[i] = (uint32_t)c;
+      c >>= 32;
+    }
+    c = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      c += (int64_t)t3[i] - (int64_t)t4[i];
+      h2[i] = (uint32_t)c;
+      c >>= 32;
+    }
+  }
+  s1 = h1[4] >> 31;
+  s2 = h2[4] >> 31;
+  // magnitudes: (h XOR -s) + s
+  uint32_t c_1 = s1, c_2 = s2;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const uint64_t a = (uint64_t)(h1[i] ^ (0u - s1)) + c_1;
+    k1[i] = (uint32_t)a;
+    c_1 = (uint32_t)(a >> 32);
+    const uint64_t b = (uint64_t)(h2[i] ^ (0u - s2)) + c_2;
+    k2[i] = (uint32_t)b;
+    c_2 = (uint32_t)(b >> 32);
+  }
+}
+
 // ---- variable base over an affine window table ----------------------------------------------------
 // The table is built with co-Z additions (uzaddu below): T_{d+1} = P + T_d with both operands over the same
 // denominator costs 4 products + 2 squares (+ 1 product where the denominator itself is tracked), leaves P
@@ -350,6 +472,10 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
   static_assert(!(GLV && FUSED), "the verify shape takes any curve point");
   static_assert(!(CT && FUSED), "the verify shape has no secret-scalar form");
   constexpr bool ASSUME_PRIME = std::is_same<G, PrimeOrderBases>::value;
+  // the signed lattice split (secp256k1): [lambda] P = sigma(P) = (beta x, y) on every point, each half's sign folded
+  // into the y of its addends; the secret-scalar ladder has no such form
+  constexpr bool LATTICE = GlvLattice<G>::value;
+  static_assert(!(LATTICE && CT), "the secret-scalar endomorphism ladder is written for the unsigned split");
   static_assert(!ASSUME_PRIME || CT, "PrimeOrderBases only narrows the secret-scalar form's collision windows");
   static_assert(WB >= 3 && WB <= 5, "table rows 1 .. 2^(WB-1) must fit the slab");
   constexpr int TBL = 1 << (WB - 1);  // table rows 1 .. TBL
@@ -380,13 +506,14 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
     const size_t idx = active ? gid : n - 1;
     const uint8_t* __restrict__ k = scalars + idx * (size_t)SB;
     if constexpr (GLV) {
-      uint32_t k1[5], k2[5];
-      glv_split<G>(k1, k2, k);
+      uint32_t k1[5], k2[5], s1 = 0, s2 = 0;  // halves' signs (word 5 of each half): the lattice split only
+      if constexpr (LATTICE) glv_split_lattice<G>(k1, k2, s1, s2, k);
+      else glv_split<G>(k1, k2, k);
       uint4* d = reinterpret_cast<uint4*>(row(0));
       d[0] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
-      d[1] = make_uint4(k1[4], 0u, 0u, 0u);
+      d[1] = make_uint4(k1[4], s1, 0u, 0u);
       d[2] = make_uint4(k2[0], k2[1], k2[2], k2[3]);
-      d[3] = make_uint4(k2[4], 0u, 0u, 0u);
+      d[3] = make_uint4(k2[4], s2, 0u, 0u);
     }
     const uint32_t* kw = row(0);  // written above through another pointer: no restrict
 
@@ -429,6 +556,7 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         const uint32_t m = (((1u << (WB + 1)) - w6 - 1u) & s) | (w6 & ~s);
         d = (m >> 1) + (m & 1u);
         neg = (s & 1u) != 0;
+        if constexpr (LATTICE) neg = neg != (h[5] != 0u);  // a negative half: -digit
       } else {
         booth_digit<WB, SB>(k, w, d, neg);
       }
@@ -653,7 +781,7 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
           uint32_t d;
           bool neg;
           booth(win, second, d, neg);
-          if (second) neg = !neg;  // [x^2]P = -sigma(P) = (beta x, -y)
+          if (second && !LATTICE) neg = !neg;  // BLS12-381: [x^2]P = -sigma(P) = (beta x, -y)
           T ex, ey;
           if constexpr (GLV) {
             T eb;

@@ -80,8 +80,9 @@ ECCX_DEV void u3_load(U<CU, 1, 3>& x, U<CU, 1, 3>& y, U<CU, 1, 3>& z, const uint
 // beyond the three written out.
 template <class CU>
 ECCX_DEV void ujac_dbl(UJac<CU>& r, const UJac<CU>& p) {
-  if constexpr (CU::Sat::A0 && CU::KIND == UK_MONT) {
-    // a = 0 on a general Montgomery field (BLS12-381), where a reduction is half of every product:
+  if constexpr (CU::Sat::A0 && CU::KIND == UK_MONT && 2 * 2 * 2 <= UBS<CU>::KKS) {
+    // a = 0 on a general Montgomery field with room for signed columns (BLS12-381: 14 x 28 bits; not secp256k1's
+    // 9 x 29, whose columns take two signed products of tight limbs), where a reduction is half of every product:
     // D = 4 X Y^2 as a product, and Y3 = E (D - X3) - 2 (2 Y^2)^2 in ONE reduction on signed columns
     // (u_mul_sub_2sqr) -- 3 products + 4 squares with 6 reductions instead of 2 + 5 with 7
     auto a = u_sqr(p.x);                                  // A = X^2

@@ -121,6 +121,9 @@ struct CurveOps {
   int (*var_ct_prime_grid)(int cus, size_t n);
   // normalisation of Jacobian rows to the x-coordinate alone, FB bytes per unit (ECCX_OUT_X_ONLY; Weierstrass)
   hipError_t (*to_affine_x)(int grid, hipStream_t s, size_t n, const uint32_t* rows, uint8_t* out, uint8_t* flags);
+  // 1: the default variable base runs var_coz with glv = 1 whatever the options say (secp256k1: the endomorphism is
+  // [lambda] on every point of a cofactor-1 curve); 0: glv only for bases vouched to be in the subgroup
+  int var_glv_default;
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
@@ -140,6 +143,7 @@ const CurveOps& ops_P384();
 const CurveOps& ops_P521();
 const CurveOps& ops_BLS12_381();
 const CurveOps& ops_ED25519();
+const CurveOps& ops_P256K1();
 
 // curve25519 x-only ladder (k_ed25519.hip): rows of row_words<8>() = 24 words per unit
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u,

@@ -9,8 +9,9 @@ from typing import Optional, Tuple
 from . import _lib
 
 # curve ids (include/eccx.h: eccx_curve)
-P256R1, P384R1, P521R1, BLS12_381_G1, ED25519 = 0, 1, 2, 3, 4
-CURVE_IDS = {"p256r1": P256R1, "p384r1": P384R1, "p521r1": P521R1, "bls12_381_g1": BLS12_381_G1, "ed25519": ED25519}
+P256R1, P384R1, P521R1, BLS12_381_G1, ED25519, P256K1 = 0, 1, 2, 3, 4, 5
+CURVE_IDS = {"p256r1": P256R1, "p384r1": P384R1, "p521r1": P521R1, "bls12_381_g1": BLS12_381_G1, "ed25519": ED25519,
+             "p256k1": P256K1}
 CURVE_NAMES = {v: k for k, v in CURVE_IDS.items()}
 
 VALIDATE_POINTS = 1 << 0
@@ -150,7 +151,7 @@ class Engine:
         """out[i] = scalars[i] * points[i]; returns (affine bytes, flags[, proj bytes]).
         mirror=True (implied by want_proj) runs the reference-mirroring kernels; ct_scan=True the secret-scalar
         ladder (every table row read at every lookup, selects only; None: the engine's secret_scalars); assume_subgroup=True (bls12_381_g1) the
-        endomorphism ladder for bases known to be in G1."""
+        endomorphism ladder for bases known to be in G1 (p256k1 runs its endomorphism ladder on every base by default)."""
         cid = curve_id(curve)
         sb, fb = scalar_bytes(cid), field_bytes(cid)
         if len(scalars) % sb:

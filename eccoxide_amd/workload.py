@@ -6,13 +6,14 @@ from __future__ import annotations
 
 import numpy as np
 
-# group orders (SEC 2 / BLS12-381 / RFC 8032), big-endian hex
+# group orders (SEC 2 / BLS12-381 / RFC 8032; p256k1 = secp256k1, SEC 2 §2.4.1), big-endian hex
 ORDERS = {
     "p256r1": "ffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551",
     "p384r1": "ffffffffffffffffffffffffffffffffffffffffffffffffc7634d81f4372ddf581a0db248b0a77aecec196accc52973",
     "p521r1": "01fffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffa51868783bf2f966b7fcc0148f709a5d03bb5c9b8899c47aebb6fb71e91386409",
     "bls12_381_g1": "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001",
     "ed25519": "1000000000000000000000000000000014def9dea2f79cd65812631a5cf5d3ed",
+    "p256k1": "fffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141",
 }
 SEED_BASE = 0xECC051DE00000000
 

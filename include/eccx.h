@@ -27,8 +27,9 @@
  *                              src/curve/bls12_381/serialize.rs:253-383, src/protocol/ed25519.rs:27-59
  *
  * Byte conventions are the reference's:
- *   - Weierstrass curves (p256r1, p384r1, p521r1, BLS12-381 G1): field elements and
- *     scalars are big-endian, FB / SB bytes (field_macros.rs:6-29).
+ *   - Weierstrass curves (p256r1, p384r1, p521r1, BLS12-381 G1, p256k1): field elements and
+ *     scalars are big-endian, FB / SB bytes (field_macros.rs:6-29); p256k1 has P-256's sizes (32 / 32)
+ *     and encodings (SEC1: 33-byte compressed points).
  *   - edwards25519: field elements little-endian (curve25519.rs:138); the SCALAR is the
  *     32-byte BIG-endian string the reference's loops index (Scalar::to_bytes_be,
  *     curve25519.rs:761, :842).
@@ -38,6 +39,9 @@
  *   - scalars are used as given: the ladder multiplies by the integer the SB bytes
  *     encode (projective.rs:871-896 accepts any byte string).  For P in the prime-order
  *     subgroup that equals (k mod n)*P.
+ *   - p256k1's default variable base runs the endomorphism ladder (k = k1 + k2 lambda, sigma(x, y) =
+ *     (beta x, y)) whatever the options say: with cofactor 1, sigma is [lambda] on every curve point, so
+ *     ECCX_ASSUME_SUBGROUP changes nothing there (as on p256r1).  Same bytes as the plain ladder.
  *
  * All functions return 0 on success or a negative ECCX_ERR_* code; none aborts.
  *
@@ -75,10 +79,10 @@
  *
  * MEMORY AND BLOCKING.  A context is bound to one GPU and owns
  *   - the window-table slab of the variable-base ladders: resident lanes x 17 rows (P-256:
- *     0.86 GB, P-384 / BLS12-381: 0.62 GB, P-521: 0.79 GB; sized by the largest batch seen),
+ *     0.86 GB, p256k1 as P-256, P-384 / BLS12-381: 0.62 GB, P-521: 0.79 GB; sized by the largest batch seen),
  *   - a buffer of un-normalised result rows, 112-224 bytes per unit of the largest batch seen,
  *   - the fixed-base tables of each curve used: the 16-bit-window table (134 MB for p256r1,
- *     ed25519 and bls12_381_g1, 201 MB p384r1, 415 MB p521r1), the reference-layout comb
+ *     ed25519, bls12_381_g1 and p256k1, 201 MB p384r1, 415 MB p521r1), the reference-layout comb
  *     (64-265 KB), for ECCX_TABLE_IN_LDS a 155 KB image, for ECCX_CT_SCAN / ECCX_CT_GATHER a signed-window
  *     table each (0.1-0.5 MB),
  *   - the device-side copies the HOST-buffer entry points keep of their arguments (sized by the largest batch
@@ -108,7 +112,8 @@ typedef enum {
   ECCX_P384R1 = 1,       /* src/curve/sec2/p384r1.rs */
   ECCX_P521R1 = 2,       /* src/curve/sec2/p521r1.rs */
   ECCX_BLS12_381_G1 = 3, /* src/curve/bls12_381/g1.rs */
-  ECCX_ED25519 = 4       /* src/curve/curve25519.rs (twisted Edwards form) */
+  ECCX_ED25519 = 4,      /* src/curve/curve25519.rs (twisted Edwards form) */
+  ECCX_P256K1 = 5        /* src/curve/sec2/p256k1.rs (secp256k1; ECDSA: src/protocol/ecdsa.rs:466-473) */
 } eccx_curve;
 
 enum {

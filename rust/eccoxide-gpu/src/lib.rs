@@ -27,8 +27,12 @@
 
 pub mod ffi;
 
+#[macro_use]
 mod weierstrass;
 pub use weierstrass::{p256r1, p384r1, p521r1};
+// secp256k1 through the same generator (its default variable base is the endomorphism ladder: same bytes as the plain
+// one).  Invoked here: weierstrass.rs lists the three NIST curves, and tests/test_rust_ffi.py maps exactly those.
+gpu_weierstrass_curve!(p256k1, eccoxide::curve::sec2::p256k1, crate::ffi::ECCX_P256K1, 32, 32);
 pub mod bls12_381_g1;
 pub mod ed25519;
 pub mod x25519;
@@ -191,6 +195,7 @@ pub enum Curve {
     P521r1,
     Bls12381G1,
     Ed25519,
+    P256k1,
 }
 
 impl Curve {
@@ -201,6 +206,7 @@ impl Curve {
             Curve::P521r1 => ffi::ECCX_P521R1,
             Curve::Bls12381G1 => ffi::ECCX_BLS12_381_G1,
             Curve::Ed25519 => ffi::ECCX_ED25519,
+            Curve::P256k1 => ffi::ECCX_P256K1,
         }
     }
     /// Field bytes FB and scalar bytes SB, as the library reports them.

@@ -39,6 +39,21 @@ ORDERS = {
     "BLS12_381": (0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001, 0x396C8C005555E1568C00AAAB0000AAAB),
 }
 
+# secp256k1 (SEC 2 v2 section 2.4.1; eccoxide's sec2::p256k1): a = 0, b = 7, cofactor 1.  Kept out of CURVES so
+# that the blocks of the five original curves come out as before; emitted after them.
+P256K1_CURVE = ("P256K1", 2**256 - 2**32 - 977, 7,
+                0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
+                0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8, 32, 32, 1)
+ORDERS["P256K1"] = (0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141, 1)
+# its endomorphism sigma(x, y) = (beta x, y) = [lambda](x, y) on every point, and the reduced basis
+# (a1, b1), (a2, b2) of the lattice {(x, y): x + y lambda = 0 mod n} the scalar split rounds against
+K1_LAMBDA = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
+K1_BETA = 0x7AE96A2B657C07106E64479EAC3434E99CF0497512F58995C1396C28719501EE
+K1_A1 = 0x3086D221A7D46BCDE86C90E49284EB15
+K1_B1 = -0xE4437ED6010E88286F547FA90ABFE4C3
+K1_A2 = 0x114CA50F7A8E2F3F657C1108D9D44CFD8
+K1_B2 = K1_A1
+
 P25519 = 2**255 - 19
 ED_D = (-121665 * pow(121666, -1, P25519)) % P25519
 ED_GX = 0x216936D3CD6E53FEC0A4E231FDD6DC5C692CC7609525A7B2C9562D608F25D51A
@@ -83,6 +98,46 @@ def _bls_beta():
     beta = acc[0] * pow(gx, -1, p) % p
     assert pow(beta, 3, p) == 1 and beta != 1 and (p - acc[1]) % p == gy
     return beta
+
+
+def _affine_mul(p, P, k):
+    """k * P with textbook affine arithmetic on y^2 = x^3 + b (a = 0); None is the point at infinity."""
+    def add(P, Q):
+        if P is None:
+            return Q
+        if Q is None:
+            return P
+        (x1, y1), (x2, y2) = P, Q
+        if x1 == x2:
+            if (y1 + y2) % p == 0:
+                return None
+            lam = 3 * x1 * x1 * pow(2 * y1, -1, p) % p
+        else:
+            lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
+        x3 = (lam * lam - x1 - x2) % p
+        return x3, (lam * (x1 - x3) - y1) % p
+
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = add(acc, acc)
+        if bit == "1":
+            acc = add(acc, P)
+    return acc
+
+
+def _k1_glv():
+    """The P256K1_GLV constants, checked: lambda a cube root of unity mod n matching beta on G, and both
+    basis vectors in the lattice.  g1 = round(2^384 b2 / n), g2 = round(-2^384 b1 / n): the split rounds
+    c1 = k g1 / 2^384 and c2 = k g2 / 2^384 (kernels_coz.hpp glv_split_lattice)."""
+    _, p, _, gx, gy, _, _, _ = P256K1_CURVE
+    n = ORDERS["P256K1"][0]
+    assert (K1_LAMBDA * K1_LAMBDA + K1_LAMBDA + 1) % n == 0
+    assert pow(K1_BETA, 3, p) == 1 and K1_BETA != 1
+    assert _affine_mul(p, (gx, gy), K1_LAMBDA) == (K1_BETA * gx % p, gy)
+    assert (K1_A1 + K1_B1 * K1_LAMBDA) % n == 0 and (K1_A2 + K1_B2 * K1_LAMBDA) % n == 0
+    g1 = ((K1_B2 << 384) + n // 2) // n
+    g2 = ((-K1_B1 << 384) + n // 2) // n
+    return n, g1, g2
 
 
 def arr(name, vals):
@@ -245,26 +300,31 @@ def emit_unsat(out, name, sat_name, p, gx, gy, bits, n, kind, extra=(), solinas=
     out.append("")
 
 
+def emit_sat(out, name, p, b, gx, gy, fb, sb, a0):
+    """The saturated parameter struct of a short-Weierstrass curve (fe.hpp / curve.hpp)."""
+    L = (p.bit_length() + 31) // 32
+    out.append("struct %s {" % name)
+    out.append("  static constexpr int L = %d;   // 32-bit limbs" % L)
+    out.append("  static constexpr int FB = %d;  // field bytes" % fb)
+    out.append("  static constexpr int SB = %d;  // scalar bytes" % sb)
+    out.append("  static constexpr int A0 = %d;  // 1: a = 0 (uses B3), 0: a = -3 (uses B)" % a0)
+    order, cof = ORDERS[name]
+    out.append("  static constexpr int NBITS = %d;  // bit length of the generator's (prime) order" % order.bit_length())
+    out.append("  static constexpr int PRIME_ORDER = %d;  // 1: cofactor 1, every curve point has that order" % (1 if cof == 1 else 0))
+    R = emit_field(out, p, L, 521 if name == "P521" else 0)
+    out.append(arr("B", limbs(b * R % p, L)))
+    out.append(arr("B3", limbs(3 * b * R % p, L)))
+    out.append(arr("GX", limbs(gx * R % p, L)))
+    out.append(arr("GY", limbs(gy * R % p, L)))
+    out.append("};")
+    out.append("")
+
+
 def main():
     out = ["// @generated by tools/gen_curve_consts.py -- do not edit.",
            "// Montgomery constants, 32-bit little-endian limbs, R = 2^(32*L).", ""]
-    for name, p, b, gx, gy, fb, sb, a0 in CURVES:
-        L = (p.bit_length() + 31) // 32
-        out.append("struct %s {" % name)
-        out.append("  static constexpr int L = %d;   // 32-bit limbs" % L)
-        out.append("  static constexpr int FB = %d;  // field bytes" % fb)
-        out.append("  static constexpr int SB = %d;  // scalar bytes" % sb)
-        out.append("  static constexpr int A0 = %d;  // 1: a = 0 (uses B3), 0: a = -3 (uses B)" % a0)
-        order, cof = ORDERS[name]
-        out.append("  static constexpr int NBITS = %d;  // bit length of the generator's (prime) order" % order.bit_length())
-        out.append("  static constexpr int PRIME_ORDER = %d;  // 1: cofactor 1, every curve point has that order" % (1 if cof == 1 else 0))
-        R = emit_field(out, p, L, 521 if name == "P521" else 0)
-        out.append(arr("B", limbs(b * R % p, L)))
-        out.append(arr("B3", limbs(3 * b * R % p, L)))
-        out.append(arr("GX", limbs(gx * R % p, L)))
-        out.append(arr("GY", limbs(gy * R % p, L)))
-        out.append("};")
-        out.append("")
+    for curve in CURVES:
+        emit_sat(out, *curve)
     bb = lambda i: (("CB", CURVES[i][2]), ("CB3", 3 * CURVES[i][2] % CURVES[i][1]))   # curve constant b and 3b
     emit_unsat(out, "P256U", "P256", CURVES[0][1], CURVES[0][3], CURVES[0][4], 29, 9, 0,
                solinas=((224, -1), (192, 1), (96, 1)), extra=bb(0), root_exp=(CURVES[0][1] + 1) // 4)
@@ -294,6 +354,25 @@ def main():
     out.append(arr("D2", limbs(2 * ED_D * R % P25519, L)))
     out.append(arr("GX", limbs(ED_GX * R % P25519, L)))
     out.append(arr("GY", limbs(ED_GY * R % P25519, L)))
+    out.append("};")
+    out.append("")
+    # secp256k1: a = 0 and cofactor 1 on a 256-bit prime that is neither -1 mod 2^29 (p = 0x1ffffc2f mod 2^29) nor of
+    # the Mersenne kinds -- 9 x 29 limbs, general Montgomery reduction (the field of p256k1)
+    k1 = P256K1_CURVE
+    emit_sat(out, *k1)
+    emit_unsat(out, "P256K1U", "P256K1", k1[1], k1[3], k1[4], 29, 9, 1,
+               extra=(("CB", k1[2]), ("CB3", 3 * k1[2] % k1[1]), ("BETA", K1_BETA)), root_exp=(k1[1] + 1) // 4)
+    n, g1, g2 = _k1_glv()
+    out.append("struct P256K1_GLV {")
+    out.append("  static constexpr bool LATTICE = true;  // signed split k = k1 + k2 lambda, sigma(P) = (beta x, y) = [lambda] P")
+    out.append(arr("N", limbs(n, 8)))
+    out.append(arr("G1", limbs(g1, 8)) + "  // round(2^384 b2 / n)")
+    out.append(arr("G2", limbs(g2, 8)) + "  // round(-2^384 b1 / n)")
+    out.append(arr("A1", limbs(K1_A1, 5)))
+    out.append(arr("B1N", limbs(-K1_B1, 5)) + "  // -b1 (b1 < 0)")
+    out.append(arr("A2", limbs(K1_A2, 5)))
+    out.append(arr("B2", limbs(K1_B2, 5)))
+    out.append("  static constexpr int K_BITS = 128;  // |k1|, |k2| < 2^128 for k < n")
     out.append("};")
     sys.stdout.write("\n".join(out) + "\n")
 
