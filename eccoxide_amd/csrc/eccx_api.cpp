@@ -68,6 +68,10 @@ struct eccx_ctx {
   static constexpr int NIO = 7;
   uint8_t* io[NIO] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t io_cap[NIO] = {0, 0, 0, 0, 0, 0, 0};
+  // working slab of eccx_ecdsa_verify_dev (u1, u2, x, ladder flags, decoded keys; grow-only), apart from the I/O slots,
+  // which the host-buffer form fills with its copies
+  uint8_t* ecdsa = nullptr;
+  size_t ecdsa_cap = 0;
   static constexpr int NEV = 10;
   hipEvent_t evs[NEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::mutex err_mu;       // err is written by whichever host thread's call failed last
@@ -150,6 +154,40 @@ int ensure_io(eccx_ctx* ctx, int slot, size_t bytes, uint8_t** out) {
     ctx->io_cap[slot] = bytes;
   }
   *out = ctx->io[slot];
+  return ECCX_OK;
+}
+
+// the ECDSA slab, carved into 16-byte aligned pieces: u1, u2 (n x SB), x (n x FB), ladder flags (n), keys (n x 2FB)
+struct EcdsaSlab {
+  uint8_t *u1, *u2, *x, *lflags, *keys;
+};
+size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+size_t ecdsa_slab_bytes(const CurveOps* ops, size_t n) {
+  const size_t sb = (size_t)ops->info.sb, fb = (size_t)ops->info.fb;
+  return 2 * align16(n * sb) + align16(n * fb) + align16(n) + n * 2 * fb;
+}
+int ensure_ecdsa(eccx_ctx* ctx, const CurveOps* ops, size_t n, EcdsaSlab* out) {
+  const size_t bytes = ecdsa_slab_bytes(ops, n);
+  {
+    std::lock_guard<std::mutex> g(ctx->scratch_mu);
+    if (bytes > ctx->ecdsa_cap) {
+      if (ctx->ecdsa) {
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        HIP_TRY(ctx, hipFree(ctx->ecdsa));
+        ctx->ecdsa = nullptr;
+        ctx->ecdsa_cap = 0;
+      }
+      HIP_TRY(ctx, hipMalloc(&ctx->ecdsa, bytes));
+      ctx->ecdsa_cap = bytes;
+    }
+  }
+  if (!out) return ECCX_OK;
+  const size_t sb = (size_t)ops->info.sb, fb = (size_t)ops->info.fb;
+  out->u1 = ctx->ecdsa;
+  out->u2 = out->u1 + align16(n * sb);
+  out->x = out->u2 + align16(n * sb);
+  out->lflags = out->x + align16(n * fb);
+  out->keys = out->lflags + align16(n);
   return ECCX_OK;
 }
 
@@ -555,6 +593,45 @@ int run_host(eccx_ctx* ctx, int curve, bool base, size_t n, const uint8_t* scala
   });
 }
 
+// the body of eccx_double_scalarmul_dev once its arguments are checked (also eccx_ecdsa_verify_dev's middle pass)
+int verify_shape(eccx_ctx* ctx, int curve, const CurveOps* ops, size_t n, const uint8_t* d_u1, const uint8_t* d_u2,
+                 const uint8_t* d_q, uint8_t* d_out, uint8_t* d_flags, uint32_t opts, hipStream_t s) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // one kernel: the ladder for u2*Q, then the 16-bit comb of u1*G onto the same point
+  int rc = ensure_comb(ctx, curve, ops, s);
+  if (rc) return rc;
+  if (!ctx->comb_u[curve]) return ECCX_ERR_HIP;
+  const int grid = ops->var_fast_grid ? ops->var_fast_grid(ctx->cus, n) : grid_for(ctx, n);
+  rc = ensure_scratch(ctx, ops->info.row5_words, grid);
+  if (rc) return rc;
+  rc = ensure_rows(ctx, ops, n);
+  if (rc) return rc;
+  const uint32_t kopts = kopts_of(opts) | ((opts & ECCX_SUBTRACT) ? K_NEGATE_B : 0u);
+  if (ops->var_coz_fused) {
+    // Weierstrass curves: the ladder over an affine window table (kernels_coz.hpp), then the generic fused
+    // kernel for the units it marked (none unless a base has order <= 16 or is not a curve point)
+    const int gridc = ops->var_coz_fused_grid(ctx->cus, n);
+    rc = ensure_scratch(ctx, ops->coz_row_words, gridc);
+    if (rc) return rc;
+    HIP_TRY(ctx, ops->var_coz_fused(gridc, s, n, d_u2, d_q, ctx->jac, d_flags, ctx->scratch, kopts, d_u1, ctx->comb_u[curve]));
+  }
+  HIP_TRY(ctx, ops->var_fused(grid, s, n, d_u2, d_q, ctx->jac, d_flags, ctx->scratch,
+                              kopts | (ops->var_coz_fused ? K_ONLY_MARKED : 0u), d_u1, ctx->comb_u[curve]));
+  // ECCX_OUT_X_ONLY: the x-coordinate alone (what ECDSA verification compares with r): FB bytes per unit, one product less
+  HIP_TRY(ctx, ((opts & ECCX_OUT_X_ONLY) ? ops->to_affine_x : ops->to_affine_var)(norm_grid(ctx, n), s, n, ctx->jac, d_out,
+                                                                                  d_flags));
+  return ECCX_OK;
+}
+
+// eccx_ecdsa_verify[_dev]: everything checkable before a device is touched
+int ecdsa_args(eccx_ctx* ctx, const CurveOps* ops, size_t digest_bytes, uint32_t opts) {
+  if (!ops->ecdsa_prepare || !ops->ecdsa_finish)
+    return arg_err(ctx, "eccx_ecdsa_verify: ECDSA is defined on p256r1, p384r1, p521r1 and p256k1");
+  if (opts & ~(uint32_t)ECCX_PUBKEY_SEC1) return arg_err(ctx, "eccx_ecdsa_verify: ECCX_PUBKEY_SEC1 is the only option");
+  if (digest_bytes > 2 * (size_t)ops->info.sb) return arg_err(ctx, "eccx_ecdsa_verify: digest_bytes must be 0 .. 2*SB");
+  return ECCX_OK;
+}
+
 int run_sharded(eccx_ctx** ctxs, int nctx, int curve, bool base, size_t n, const uint8_t* scalars,
                 const uint8_t* points, uint8_t* out, uint8_t* flags, uint32_t opts) {
   const CurveOps* ops = ops_of(curve);
@@ -638,6 +715,7 @@ void eccx_shutdown(eccx_ctx* ctx) {
   if (ctx->jac) (void)hipFree(ctx->jac);
   for (auto& b : ctx->io)
     if (b) (void)hipFree(b);
+  if (ctx->ecdsa) (void)hipFree(ctx->ecdsa);
   for (auto& e : ctx->evs)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -694,7 +772,7 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc = ensure_rows(ctx, ops, max_n);  // every entry point writes un-normalised rows first
   if (rc) return rc;
-  if (what & ECCX_PREP_VAR) {  // window-table slab of the default ladder (also the fused double-scalar kernel)
+  if (what & (ECCX_PREP_VAR | ECCX_PREP_ECDSA)) {  // window-table slab of the default ladder (also the fused double-scalar kernel)
     const int grid = ops->var_fast_grid ? ops->var_fast_grid(ctx->cus, max_n) : grid_for(ctx, max_n);
     rc = ensure_scratch(ctx, ops->info.row5_words, grid);
     if (rc) return rc;
@@ -731,6 +809,10 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
       if (rc) return rc;
     }
   }
+  if ((what & ECCX_PREP_ECDSA) && ops->ecdsa_prepare) {  // eccx_ecdsa_verify's own working slab
+    rc = ensure_ecdsa(ctx, ops, max_n, nullptr);
+    if (rc) return rc;
+  }
   // slab of the reference-mirroring ladder (also what ECCX_CT_SCAN runs on a curve without a scanning fast ladder)
   const bool mirror_slab = (what & ECCX_PREP_MIRROR) || ((what & ECCX_PREP_CT) && !ops->var_ct);
   if (mirror_slab && ops->info.row_words) {
@@ -748,7 +830,7 @@ size_t eccx_device_bytes(const eccx_ctx* ctx) {
   std::lock_guard<std::mutex> g2(c->scratch_mu);
   size_t io = 0;
   for (size_t b : c->io_cap) io += b;
-  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io;
+  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap;
 }
 
 int eccx_scalarmul_var_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points,
@@ -1025,36 +1107,9 @@ int eccx_double_scalarmul_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_
     ctx->set_err("eccx_double_scalarmul: ECCX_CT_SCAN is not accepted (signature verification handles public data)");
     return ECCX_ERR_ARG;
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // one kernel: the ladder for u2*Q, then the 16-bit comb of u1*G onto the same point
-  hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
-  int rc = ensure_comb(ctx, curve, ops, s);
-  if (rc) return rc;
-  if (!ctx->comb_u[curve]) return ECCX_ERR_HIP;
-  const int grid = ops->var_fast_grid ? ops->var_fast_grid(ctx->cus, n) : grid_for(ctx, n);
-  rc = ensure_scratch(ctx, ops->info.row5_words, grid);
-  if (rc) return rc;
-  rc = ensure_rows(ctx, ops, n);
-  if (rc) return rc;
-  const uint32_t kopts = kopts_of(opts) | ((opts & ECCX_SUBTRACT) ? K_NEGATE_B : 0u);
-  if (ops->var_coz_fused) {
-    // Weierstrass curves: the ladder over an affine window table (kernels_coz.hpp), then the generic fused
-    // kernel for the units it marked (none unless a base has order <= 16 or is not a curve point)
-    const int gridc = ops->var_coz_fused_grid(ctx->cus, n);
-    rc = ensure_scratch(ctx, ops->coz_row_words, gridc);
-    if (rc) return rc;
-    HIP_TRY(ctx, ops->var_coz_fused(gridc, s, n, static_cast<const uint8_t*>(d_u2), static_cast<const uint8_t*>(d_q), ctx->jac,
-                                    static_cast<uint8_t*>(d_flags), ctx->scratch, kopts, static_cast<const uint8_t*>(d_u1),
-                                    ctx->comb_u[curve]));
-  }
-  HIP_TRY(ctx, ops->var_fused(grid, s, n, static_cast<const uint8_t*>(d_u2), static_cast<const uint8_t*>(d_q), ctx->jac,
-                              static_cast<uint8_t*>(d_flags), ctx->scratch, kopts | (ops->var_coz_fused ? K_ONLY_MARKED : 0u),
-                              static_cast<const uint8_t*>(d_u1), ctx->comb_u[curve]));
-  // ECCX_OUT_X_ONLY: the x-coordinate alone (what ECDSA verification compares with r): FB bytes per unit, one product less
-  HIP_TRY(ctx, ((opts & ECCX_OUT_X_ONLY) ? ops->to_affine_x : ops->to_affine_var)(norm_grid(ctx, n), s, n, ctx->jac,
-                                                                                  static_cast<uint8_t*>(d_out),
-                                                                                  static_cast<uint8_t*>(d_flags)));
-  return ECCX_OK;
+  return verify_shape(ctx, curve, ops, n, static_cast<const uint8_t*>(d_u1), static_cast<const uint8_t*>(d_u2),
+                      static_cast<const uint8_t*>(d_q), static_cast<uint8_t*>(d_out), static_cast<uint8_t*>(d_flags), opts,
+                      static_cast<hipStream_t>(stream));
 }
 
 int eccx_double_scalarmul(eccx_ctx* ctx, int curve, size_t n, const uint8_t* u1, const uint8_t* u2,
@@ -1079,6 +1134,65 @@ int eccx_double_scalarmul(eccx_ctx* ctx, int curve, size_t n, const uint8_t* u1,
   return host_pipeline(ctx, n, ins, 3, outs, 2, /*chunked=*/true, [&](size_t lo, size_t cnt) {
     return eccx_double_scalarmul_dev(ctx, curve, cnt, d_u1 + lo * sb, d_u2 + lo * sb, d_q + lo * pb, d_o + lo * ob, d_f + lo, opts,
                                      ctx->stream);
+  });
+}
+
+int eccx_ecdsa_verify_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_digests, size_t digest_bytes, const void* d_sigs,
+                          const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ctx) return ECCX_ERR_ARG;
+  if (!ops) return curve_err(ctx);
+  int rc = ecdsa_args(ctx, ops, digest_bytes, opts);
+  if (rc) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!d_digests || !d_sigs || !d_pubkeys || !d_verdicts) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EcdsaSlab w;
+  rc = ensure_ecdsa(ctx, ops, n, &w);
+  if (rc) return rc;
+  const uint8_t* sigs = static_cast<const uint8_t*>(d_sigs);
+  const uint8_t* keys = static_cast<const uint8_t*>(d_pubkeys);
+  uint8_t* verdicts = static_cast<uint8_t*>(d_verdicts);
+  const uint8_t* key_flags = nullptr;
+  if (opts & ECCX_PUBKEY_SEC1) {  // decoded into the slab; the decoder's flags park in the verdicts until the next pass
+    HIP_TRY(ctx, ops->decompress(flat_grid(ctx, n), s, n, keys, w.keys, verdicts));
+    keys = w.keys;
+    key_flags = verdicts;
+  }
+  HIP_TRY(ctx, ops->ecdsa_prepare(flat_grid(ctx, n), s, n, static_cast<const uint8_t*>(d_digests), (int)digest_bytes, sigs,
+                                  key_flags, w.u1, w.u2, verdicts));
+  // the verify shape; the key is validated there (flag 2: non-canonical or off the curve; the identity has no affine
+  // form but (0, 0), which is off every curve served here)
+  rc = verify_shape(ctx, curve, ops, n, w.u1, w.u2, keys, w.x, w.lflags, ECCX_VALIDATE_POINTS | ECCX_OUT_X_ONLY, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, ops->ecdsa_finish(flat_grid(ctx, n), s, n, sigs, w.x, w.lflags, verdicts));
+  return ECCX_OK;
+}
+
+int eccx_ecdsa_verify(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests, size_t digest_bytes, const uint8_t* sigs,
+                      const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ctx) return ECCX_ERR_ARG;
+  if (!ops) return curve_err(ctx);
+  int rc = ecdsa_args(ctx, ops, digest_bytes, opts);
+  if (rc) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!digests || !sigs || !pubkeys || !verdicts) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t sb = (size_t)ops->info.sb, db = digest_bytes ? digest_bytes : sb;
+  const size_t kb = (opts & ECCX_PUBKEY_SEC1) ? (size_t)ops->enc_bytes : 2 * (size_t)ops->info.fb;
+  uint8_t *d_d = nullptr, *d_s = nullptr, *d_k = nullptr, *d_v = nullptr;
+  rc = ensure_io(ctx, IO_K, n * db, &d_d);
+  if (!rc) rc = ensure_io(ctx, IO_O, n * 2 * sb, &d_s);
+  if (!rc) rc = ensure_io(ctx, IO_P, n * kb, &d_k);
+  if (!rc) rc = ensure_io(ctx, IO_F, n, &d_v);
+  if (rc) return rc;
+  const HostIn ins[3] = {{d_d, digests, db}, {d_s, sigs, 2 * sb}, {d_k, pubkeys, kb}};
+  const HostOut outs[1] = {{verdicts, d_v, 1}};
+  return host_pipeline(ctx, n, ins, 3, outs, 1, /*chunked=*/true, [&](size_t lo, size_t cnt) {
+    return eccx_ecdsa_verify_dev(ctx, curve, cnt, d_d + lo * db, digest_bytes, d_s + lo * 2 * sb, d_k + lo * kb, d_v + lo, opts,
+                                 ctx->stream);
   });
 }
 

@@ -13,4 +13,5 @@
   do {                                      \
     (t).var_glv_default = ECCX_P256K1_GLV;  \
   } while (0)
+#define ECCX_ORDER P256K1_ORD
 #include "k_weierstrass.inc"

@@ -7,9 +7,14 @@
 //   ECCX_EXTRA_OPS(t) (optional) statement filling further members of the CurveOps `t`
 //   ECCX_GLV_PARAMS  (optional) the curve's endomorphism constants: instantiates the GLV form of the
 //                    affine-table ladder (kernels_coz.hpp) beside the plain one
+//   ECCX_ORDER       (optional) the struct of the group order n (curve_consts.inc, e.g. P256_ORD): instantiates the
+//                    ECDSA verification passes (kernels_ecdsa.hpp)
 #include "kernels_codec.hpp"
 #include "kernels_coz.hpp"
 #include "launch.hpp"
+#ifdef ECCX_ORDER
+#include "kernels_ecdsa.hpp"
+#endif
 #ifndef ECCX_CODEC_FORMAT
 #define ECCX_CODEC_FORMAT FORMAT_SEC1
 #endif
@@ -200,6 +205,20 @@ hipError_t compress_raw_(int grid, hipStream_t s, size_t n, const uint8_t* xy, c
     return hipErrorNotSupported;
   }
 }
+#ifdef ECCX_ORDER
+static_assert(ECCX_ORDER::SB == ECCX_CURVE::SB && ECCX_CURVE::FB == ECCX_CURVE::SB, "x-coordinates and scalars share a width");
+hipError_t ecdsa_prepare_(int grid, hipStream_t s, size_t n, const uint8_t* digests, int digest_bytes, const uint8_t* sigs,
+                          const uint8_t* key_flags, uint8_t* u1, uint8_t* u2, uint8_t* verdicts) {
+  hipLaunchKernelGGL(k_ecdsa_prepare<ECCX_ORDER>, dim3(grid), dim3(WG), 0, s, n, digests, digest_bytes, sigs, key_flags, u1, u2,
+                     verdicts);
+  return hipGetLastError();
+}
+hipError_t ecdsa_finish_(int grid, hipStream_t s, size_t n, const uint8_t* sigs, const uint8_t* xs, const uint8_t* lflags,
+                         uint8_t* verdicts) {
+  hipLaunchKernelGGL(k_ecdsa_finish<ECCX_ORDER>, dim3(grid), dim3(WG), 0, s, n, sigs, xs, lflags, verdicts);
+  return hipGetLastError();
+}
+#endif
 }  // namespace
 const CurveOps& ECCX_OPS_NAME() {
   static const CurveOps o = [] {
@@ -229,6 +248,10 @@ const CurveOps& ECCX_OPS_NAME() {
     t.var_ct_prime_grid = var_ct_prime_grid_;
     t.var_ct_grid = var_ct_grid_;
     t.to_affine_x = to_affine_x_;
+#ifdef ECCX_ORDER
+    t.ecdsa_prepare = ecdsa_prepare_;
+    t.ecdsa_finish = ecdsa_finish_;
+#endif
 #ifdef ECCX_EXTRA_OPS
     ECCX_EXTRA_OPS(t);
 #endif

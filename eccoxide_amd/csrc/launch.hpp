@@ -124,6 +124,14 @@ struct CurveOps {
   // 1: the default variable base runs var_coz with glv = 1 whatever the options say (secp256k1: the endomorphism is
   // [lambda] on every point of a cofactor-1 curve); 0: glv only for bases vouched to be in the subgroup
   int var_glv_default;
+  // ECDSA verification (kernels_ecdsa.hpp; null where the curve has no ECDSA): ecdsa_prepare checks r, s, converts the
+  // digests (digest_bytes == 0: SB-byte scalars as they are) and writes u1, u2 (SB bytes each) and the pre-verdicts;
+  // key_flags (may be null, may alias verdicts) are the SEC1 decoder's.  ecdsa_finish folds x (FB bytes) and the
+  // ladder's flags into the verdicts.
+  hipError_t (*ecdsa_prepare)(int grid, hipStream_t s, size_t n, const uint8_t* digests, int digest_bytes, const uint8_t* sigs,
+                              const uint8_t* key_flags, uint8_t* u1, uint8_t* u2, uint8_t* verdicts);
+  hipError_t (*ecdsa_finish)(int grid, hipStream_t s, size_t n, const uint8_t* sigs, const uint8_t* xs, const uint8_t* lflags,
+                             uint8_t* verdicts);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above

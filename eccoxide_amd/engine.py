@@ -26,8 +26,13 @@ CT_SCAN = 1 << 8
 ASSUME_SUBGROUP = 1 << 9
 CT_GATHER = 1 << 10
 OUT_X_ONLY = 1 << 11
+PUBKEY_SEC1 = 1 << 12
 PREP_VAR, PREP_BASE, PREP_BASE_LDS, PREP_MIRROR, PREP_CT, PREP_CT_GATHER, PREP_HOST = 1, 2, 4, 8, 16, 32, 64
+PREP_ECDSA = 128
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
+# ECDSA verdicts (include/eccx.h: ECCX_SIG_*)
+SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
+ECDSA_CURVES = (P256R1, P384R1, P521R1, P256K1)
 
 
 class EccxError(RuntimeError):
@@ -134,12 +139,14 @@ class Engine:
                                            (PREP_BASE if base else 0) | (PREP_BASE_LDS if base_lds else 0)
                                            | (PREP_CT if ct else 0) | (PREP_CT_GATHER if ct_gather else 0)))
 
-    def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False):
+    def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
+                ecdsa: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
-        secret-scalar (ECCX_CT_SCAN) variable-base ladder."""
+        secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
-                                           | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)))
+                                           | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
+                                           | (PREP_ECDSA if ecdsa else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -225,6 +232,60 @@ class Engine:
                                              | (OUT_X_ONLY if x_only else 0))
         self._check(rc)
         return out.raw[: n * width], flags.raw[:n]
+
+    def _ecdsa_widths(self, curve, digest_bytes, sec1):
+        cid = curve_id(curve)
+        if cid not in ECDSA_CURVES:
+            raise ValueError("ECDSA is defined on p256r1, p384r1, p521r1 and p256k1")
+        sb, fb = scalar_bytes(cid), field_bytes(cid)
+        kb = self.compressed_bytes(cid) if sec1 else 2 * fb
+        return cid, sb, kb
+
+    def ecdsa_verify(self, curve, digests: bytes, sigs: bytes, pubkeys: bytes, *, digest_bytes: Optional[int] = None,
+                     sec1: bool = False) -> bytes:
+        """ECDSA verification of a batch (eccx_ecdsa_verify; src/protocol/ecdsa.rs verify / verify_hashed).
+        digests: n x digest_bytes message digests (bits2int applied on the GPU), or with digest_bytes=0 n x SB scalars
+        used as they are; digest_bytes=None infers it from len(digests) / n.  sigs: n x 2SB r || s; pubkeys: n x 2FB
+        affine x || y, or n x (FB + 1) SEC1 compressed with sec1=True.  Returns n verdict bytes (SIG_*)."""
+        cid, sb, kb = self._ecdsa_widths(curve, digest_bytes, sec1)
+        if len(sigs) % (2 * sb):
+            raise ValueError(f"sigs must be n x {2 * sb} bytes")
+        n = len(sigs) // (2 * sb)
+        if digest_bytes is None:
+            if n == 0 or len(digests) % n:
+                raise ValueError("cannot infer digest_bytes: give it explicitly")
+            digest_bytes = len(digests) // n
+        db = int(digest_bytes)
+        if len(digests) != n * (db or sb) or len(pubkeys) != n * kb:
+            raise ValueError(f"digests must be n x {db or sb} bytes and pubkeys n x {kb} bytes")
+        verdicts = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_ecdsa_verify(self._ctx, cid, n, digests, db, sigs, pubkeys, verdicts,
+                                                PUBKEY_SEC1 if sec1 else 0))
+        return verdicts.raw[:n]
+
+    def ecdsa_verify_t(self, curve, digests, sigs, pubkeys, verdicts=None, *, digest_bytes: Optional[int] = None,
+                       sec1: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of ecdsa_verify (torch.uint8 CUDA tensors; eccx_ecdsa_verify_dev): enqueued on `stream`
+        (default: torch's current stream), returns the n-byte verdict tensor."""
+        import torch
+
+        cid, sb, kb = self._ecdsa_widths(curve, digest_bytes, sec1)
+        n = self._units(sigs, 2 * sb, "sigs")
+        if digest_bytes is None:
+            if n == 0 or digests.numel() % n:
+                raise ValueError("cannot infer digest_bytes: give it explicitly")
+            digest_bytes = digests.numel() // n
+        db = int(digest_bytes)
+        if verdicts is None:
+            verdicts = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
+        self._tensors(n, ("digests", digests, db or sb), ("sigs", sigs, 2 * sb), ("pubkeys", pubkeys, kb),
+                      ("verdicts", verdicts, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(sigs.device).cuda_stream
+        self._check(self._lib.eccx_ecdsa_verify_dev(self._ctx, cid, n, digests.data_ptr(), db, sigs.data_ptr(),
+                                                    pubkeys.data_ptr(), verdicts.data_ptr(), PUBKEY_SEC1 if sec1 else 0,
+                                                    stream))
+        return verdicts
 
     def compressed_bytes(self, curve) -> int:
         """Bytes per compressed point: FB + 1 (SEC1), 48 (zcash G1), 32 (RFC 8032)."""

@@ -19,6 +19,7 @@
  *   eccx_comb_table            COMB_TABLE constants              src/params/comb/<curve>.rs
  *   eccx_point_add[_dev]       impl Add / Sub / Neg, CurveGroup::double   curve_macros.rs:297-411, group.rs:28-70
  *   eccx_double_scalarmul[_dev]  u1*G + u2*Q                     src/protocol/ecdsa.rs:215, ed25519.rs:145
+ *   eccx_ecdsa_verify[_dev]      ECDSA verification              src/protocol/ecdsa.rs:200-222
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
@@ -165,6 +166,7 @@ enum {
                                       digit steers the wavefront's register crossbar, whose time was MEASURED the same for
                                       every index pattern tried (profiles/r03_select_rates.jsonl) -- not an architectural
                                       guarantee, hence opt-in.  About 1.4x faster than the scan. */
+  ECCX_PUBKEY_SEC1 = 1u << 12,     /* eccx_ecdsa_verify: public keys are SEC1 compressed, FB + 1 bytes each */
   ECCX_OUT_X_ONLY = 1u << 11,      /* eccx_double_scalarmul: write the x-coordinate alone, FB bytes per unit (`out` is then
                                       n x FB): Point::to_affine_x_ct (src/curve/projective.rs:690), which is all ECDSA
                                       verification reads (src/protocol/ecdsa.rs:383).  Weierstrass curves. */
@@ -188,6 +190,8 @@ enum {
   ECCX_PREP_BASE_LDS = 1u << 2, /* ECCX_TABLE_IN_LDS image (edwards25519) */
   ECCX_PREP_MIRROR = 1u << 3,   /* ECCX_MIRROR_REFERENCE / proj: slab of the mirror ladder */
   ECCX_PREP_HOST = 1u << 6,     /* eccx_reserve: the device-side copies the HOST-buffer entry points keep of their arguments */
+  ECCX_PREP_ECDSA = 1u << 7,    /* eccx_reserve: the working slabs of eccx_ecdsa_verify (u1, u2, x, flags, decoded keys) and
+                                   the slabs of the verify-shape ladder it runs (as ECCX_PREP_VAR) */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -196,6 +200,14 @@ enum {
 
 /* flag values written per unit */
 enum { ECCX_FLAG_FINITE = 0, ECCX_FLAG_INFINITY = 1, ECCX_FLAG_REJECTED = 2 };
+
+/* ECDSA verdicts (eccx_ecdsa_verify), one byte per signature */
+enum {
+  ECCX_SIG_INVALID = 0,   /* the equation fails: x(R) mod n != r, or R = u1*G + u2*Q is the identity */
+  ECCX_SIG_VALID = 1,
+  ECCX_SIG_MALFORMED = 2, /* r or s is 0 or >= n (Signature::from_bytes), or a digest_bytes == 0 scalar is >= n */
+  ECCX_SIG_BAD_KEY = 3    /* the public key is non-canonical, off the curve or the identity, or its SEC1 bytes do not decode */
+};
 
 typedef struct eccx_ctx eccx_ctx;
 
@@ -277,6 +289,28 @@ int eccx_double_scalarmul(eccx_ctx* ctx, int curve, size_t n, const uint8_t* u1,
  * `stream` (NULL = HIP's default stream), no synchronisation -- as eccx_scalarmul_var_dev. */
 int eccx_double_scalarmul_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_u1, const void* d_u2, const void* d_q,
                               void* d_out, void* d_flags, uint32_t opts, void* stream);
+
+/* ECDSA verification, batched (src/protocol/ecdsa.rs verify / verify_hashed, :200-222).
+ *   curves  : p256r1, p384r1, p521r1, p256k1 (others: ECCX_ERR_ARG)
+ *   digests : n x digest_bytes message digests, converted with the reference's digest_to_scalar (SEC1 bits2int: the
+ *             leftmost qlen bits, then reduced mod n; :332-352); digest_bytes is 0 .. 2*SB (SHA-224 to SHA-512 on
+ *             every curve, 66-byte input on p521r1), anything else is ECCX_ERR_ARG.
+ *             digest_bytes == 0: n x SB big-endian scalars z used as they are (verify_hashed; z >= n is malformed)
+ *   sigs    : n x 2*SB, r || s big-endian (Signature::to_bytes)
+ *   pubkeys : n x 2*FB affine x || y, or n x (FB + 1) SEC1 compressed with ECCX_PUBKEY_SEC1
+ *   verdicts: n bytes, one ECCX_SIG_* per signature.  Where several apply: MALFORMED before BAD_KEY before the
+ *             equation.
+ * Public keys are ALWAYS validated (canonical coordinates, on the curve, not the identity): the reference gets a valid
+ * Point by construction, bytes handed to this call are untrusted.  Low-S is not enforced: s and n - s both verify, as
+ * in the reference.  On the GPU: one pass checks r and s, converts the digest and computes w = s^-1 (division steps
+ * modulo n), u1 = e*w, u2 = r*w; under ECCX_PUBKEY_SEC1 the keys are decoded first; the verify shape of
+ * eccx_double_scalarmul runs with ECCX_VALIDATE_POINTS | ECCX_OUT_X_ONLY; a last pass compares x(R) mod n with r.
+ * Options: ECCX_PUBKEY_SEC1 only (ECCX_CT_SCAN and the rest: ECCX_ERR_ARG).  The _dev form enqueues on `stream`
+ * without synchronising and uses the context's ECDSA slabs (grow-only; eccx_reserve with ECCX_PREP_ECDSA sizes them). */
+int eccx_ecdsa_verify(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests, size_t digest_bytes,
+                      const uint8_t* sigs, const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts);
+int eccx_ecdsa_verify_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_digests, size_t digest_bytes,
+                          const void* d_sigs, const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

@@ -41,6 +41,7 @@ pub const ECCX_CT_SCAN: u32 = 1 << 8;
 pub const ECCX_ASSUME_SUBGROUP: u32 = 1 << 9;
 pub const ECCX_CT_GATHER: u32 = 1 << 10;
 pub const ECCX_OUT_X_ONLY: u32 = 1 << 11;
+pub const ECCX_PUBKEY_SEC1: u32 = 1 << 12;
 
 // eccx_prepare / eccx_reserve
 pub const ECCX_PREP_VAR: u32 = 1 << 0;
@@ -52,11 +53,18 @@ pub const ECCX_PREP_CT_GATHER: u32 = 1 << 5;
 pub const ECCX_PREP_HOST: u32 = 1 << 6;
 pub const ECCX_PREP_CT_GATHER: u32 = 1 << 5;
 pub const ECCX_PREP_CT: u32 = 1 << 4; // ECCX_CT_SCAN: the secret-scalar fixed-base table / variable-base slabs
+pub const ECCX_PREP_ECDSA: u32 = 1 << 7; // eccx_ecdsa_verify's working slabs
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
 pub const ECCX_FLAG_INFINITY: u8 = 1;
 pub const ECCX_FLAG_REJECTED: u8 = 2;
+
+// ECDSA verdicts, one byte per signature (eccx_ecdsa_verify)
+pub const ECCX_SIG_INVALID: u8 = 0;
+pub const ECCX_SIG_VALID: u8 = 1;
+pub const ECCX_SIG_MALFORMED: u8 = 2;
+pub const ECCX_SIG_BAD_KEY: u8 = 3;
 
 #[link(name = "eccx")]
 extern "C" {
@@ -96,6 +104,13 @@ extern "C" {
     pub fn eccx_double_scalarmul_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_u1: *const c_void,
                                      d_u2: *const c_void, d_q: *const c_void, d_out: *mut c_void,
                                      d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+
+    // ECDSA verification, batched                           protocol::ecdsa::verify / verify_hashed
+    pub fn eccx_ecdsa_verify(ctx: *mut eccx_ctx, curve: c_int, n: usize, digests: *const u8, digest_bytes: usize,
+                             sigs: *const u8, pubkeys: *const u8, verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_ecdsa_verify_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_digests: *const c_void, digest_bytes: usize,
+                                 d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
+                                 stream: *mut c_void) -> c_int;
 
     // X25519 over a batch                                    protocol::x25519::x25519
     pub fn eccx_x25519(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,

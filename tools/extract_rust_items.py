@@ -20,7 +20,8 @@ FILES = ["src/lib.rs", "src/curve/mod.rs", "src/curve/group.rs", "src/curve/fiel
          "src/curve/fiat/field_macros.rs", "src/curve/fiat/curve_macros.rs", "src/curve/sec2/mod.rs", "src/curve/sec2/p256r1.rs",
          "src/curve/sec2/p384r1.rs", "src/curve/sec2/p521r1.rs", "src/curve/curve25519.rs", "src/curve/bls12_381/mod.rs",
          "src/curve/bls12_381/g1.rs", "src/curve/bls12_381/fp.rs", "src/curve/bls12_381/scalar.rs", "src/curve/bls12_381/serialize.rs",
-         "src/protocol/x25519.rs", "src/protocol/ed25519.rs"]
+         "src/protocol/x25519.rs", "src/protocol/ed25519.rs", "src/protocol/ecdsa.rs",
+         "src/protocol/mod.rs"]
 PAT = re.compile(r"\bpub(?:\([a-z ]+\))?\s+(?:const\s+)?(fn|struct|enum|trait|mod|const|type|use)\s+([A-Za-z_][A-Za-z0-9_]*)")
 
 

@@ -374,6 +374,21 @@ def main():
     out.append(arr("B2", limbs(K1_B2, 5)))
     out.append("  static constexpr int K_BITS = 128;  // |k1|, |k2| < 2^128 for k < n")
     out.append("};")
+    # the scalar fields of the ECDSA curves (kernels_ecdsa.hpp): arithmetic modulo the group order n with fe.hpp's general
+    # word-by-word Montgomery product and inv_gcd.hpp's division steps.  FB is the scalar size here, so the byte I/O of
+    # fe.hpp moves SB-byte scalars.  The P-521 order is a general 521-bit modulus (not Mersenne): 17 limbs, Montgomery.
+    for name in ("P256", "P384", "P521", "P256K1"):
+        n = ORDERS[name][0]
+        sb = next(c[6] for c in CURVES + [P256K1_CURVE] if c[0] == name)
+        L = (n.bit_length() + 31) // 32
+        out.append("")
+        out.append("struct %s_ORD {  // n, the order of the generator of %s" % (name, name))
+        out.append("  static constexpr int L = %d;   // 32-bit limbs" % L)
+        out.append("  static constexpr int FB = %d;  // bytes of an element (= SB)" % sb)
+        out.append("  static constexpr int SB = %d;  // scalar bytes" % sb)
+        out.append("  static constexpr int NBITS = %d;  // qlen: bits2int keeps this many leading bits of a digest" % n.bit_length())
+        emit_field(out, n, L)
+        out.append("};")
     sys.stdout.write("\n".join(out) + "\n")
 
 
