@@ -311,6 +311,8 @@ ECCX_DEV void ujac_madd_signed(UJac<CU>& r, bool& h_zero, bool& r_zero, const UJ
     r.y = u_fit<1, 3>(u_mul_add(rr, u_sub(v, x3), u_neg(p.y), hhh));  // one reduction for both products
   } else if constexpr (UB<CU>::SPARSE) {
     r.y = u_mul_sub(rr, u_sub(v, x3), p.y, hhh);
+  } else if constexpr (UBS<CU>::DENSE) {
+    r.y = u_mul_sub(rr, u_reduce(u_sub(v, x3)), p.y, hhh);  // P-256: tight operands, one reduction (K 1*1 per side)
   } else {
     auto y3a = u_mul(rr, u_sub(v, x3));
     auto y1h = u_mul(p.y, hhh);
@@ -765,15 +767,31 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         bool step_done;
         if (fix_pending || sub < WB) {
           UJac<CU> t;
-          ujac_dbl<CU>(t, q);
-          if (fix_pending) {
-            u_select(q.x, fix_lane, t.x, q.x);
-            u_select(q.y, fix_lane, t.y, q.y);
-            u_select(q.z, fix_lane, t.z, q.z);
-            fix_pending = false;
-            fix_lane = false;
-          } else {
+          if constexpr (UBS<CU>::DENSE) {
+            // P-256: the merged doubling, and the equal-points fix-up in a wave-uniform branch of its own.  Its
+            // selects are asm (u_cmov_ct), which the compiler does not hoist, so the common path is q = t (written
+            // with ?:, the branch is if-converted into 3 N v_cndmask that every doubling runs).
+            ujac_dbl_merged<CU>(t, q);
+            if (fix_pending) {
+              const uint64_t keep = ct_mask(!fix_lane);  // lanes without the fix-up keep q
+              u_cmov_ct(t.x, keep, q.x);
+              u_cmov_ct(t.y, keep, q.y);
+              u_cmov_ct(t.z, keep, q.z);
+              fix_pending = false;
+              fix_lane = false;
+            }
             q = t;
+          } else {
+            ujac_dbl<CU>(t, q);
+            if (fix_pending) {
+              u_select(q.x, fix_lane, t.x, q.x);
+              u_select(q.y, fix_lane, t.y, q.y);
+              u_select(q.z, fix_lane, t.z, q.z);
+              fix_pending = false;
+              fix_lane = false;
+            } else {
+              q = t;
+            }
           }
           step_done = true;
         } else {

@@ -46,8 +46,9 @@
 //     mul_sub_2sqr   a*b - 2*c^2 + p on SIGNED columns (P-384, whose sparse reduction is signed anyway;
 //                    BLS12-381): the subtracted product goes in with v_mad_i64_i32 against negated
 //                    limbs, each side of a column within 63 bits (K1K2 <= UBS::KKS per product), p
-//                    added above R so that the result is in (0, 3p).  P-256 (9 x 29 bits) and P-521
-//                    have no room for either form.
+//                    added above R so that the result is in (0, 3p).  P-256 (9 x 29 bits) has room for
+//                    one product of tight operands per side (UBS::KKS = 2): its core folds m*(p+1) by
+//                    the four non-zero digits of p + 1 into the same signed columns.  P-521 has none.
 #pragma once
 #include "fe.hpp"
 
@@ -378,6 +379,56 @@ ECCX_DEV void u_mul_sub_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N]
   for (int i = 0; i < N; ++i) r[i] = t[i];
 }
 
+// The same for p = -1 mod 2^B without the sparse form (P-256): m*(p+1) enters as its non-zero digits, as in
+// u_mul_core_mont, on columns read as signed.  Column bound, either side below 2^63 = 32 * 2^(2B) for B = 29:
+//   positive  a*b: at most N = 9 products below K1*K2 * 2^(2B) (K1*K2 <= UBS::KKS = 2: 18 * 2^(2B)); m*(p+1): at
+//             most 4 products below 2^(2B) (digits 3, 6, 7, 8 of p + 1); a digit of p (< 2^B); carry in < 2^(63-B)
+//             -> below 22 * 2^(2B) + 2^35
+//   negative  c*d (or 2 c^2): at most 9 products below K3*K4 * 2^(2B) (or 2 K3^2 <= KKS: 18 * 2^(2B)); carry in
+//             above -2^(63-B)
+// and the low limb is taken as the Montgomery factor (-p^-1 mod 2^B = 1) exactly as in the unsigned core.
+template <class C, bool NEG_SQ>
+ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N],
+                                 const uint32_t (&c)[C::N], const uint32_t (&d)[C::N]) {
+  constexpr int N = C::N;
+  static_assert(C::KIND == UK_MONT_PP1 && C::SPARSE_N == 0, "p = -1 mod 2^B with p + 1 as plain digits");
+  uint32_t m[N], t[N];
+  int32_t nc[N];  // -c (NEG_SQ: -2c)
+#pragma unroll
+  for (int i = 0; i < N; ++i) nc[i] = NEG_SQ ? -(int32_t)(c[i] << 1) : -(int32_t)c[i];
+  uint64_t acc = 0;
+  UMacQ<false> qa;
+  UMacQ<true> qm;
+#pragma unroll
+  for (int k = 0; k < 2 * N - 1; ++k) {
+    const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
+    if (k >= N && C::P[k - N] != 0) acc += (uint64_t)C::P[k - N];  // + p*R
+#pragma unroll
+    for (int i = lo; i <= hi; ++i) qa.push(acc, a[i], b[k - i]);
+    qa.flush(acc);
+    if constexpr (NEG_SQ) {
+#pragma unroll
+      for (int i = lo; 2 * i < k; ++i) smad1_v(acc, nc[i], (int32_t)(c[k - i] << 1));
+      if ((k & 1) == 0) smad1_v(acc, nc[k / 2], (int32_t)c[k / 2]);
+    } else {
+#pragma unroll
+      for (int i = lo; i <= hi; ++i) smad1_v(acc, nc[i], (int32_t)d[k - i]);
+    }
+#pragma unroll
+    for (int i = lo; i <= (k < N ? k - 1 : N - 1); ++i) {
+      if (C::PP1[k - i] != 0) qm.push(acc, m[i], C::PP1[k - i]);
+    }
+    qm.flush(acc);
+    if (k < N) m[k] = (uint32_t)acc & C::MASK;
+    else t[k - N] = (uint32_t)acc & C::MASK;
+    acc = (uint64_t)((int64_t)acc >> C::B);
+  }
+  acc += (uint64_t)C::P[N - 1];
+  t[N - 1] = (uint32_t)acc;
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = t[i];
+}
+
 // Mersenne product / square (kind 2), p = 2^k - 1 with B*N - k = S: the product's upper half
 // has weight 2^(B*N) = 2^S (mod p), so a_i * b_j with i + j >= N is accumulated into column
 // i + j - N times 2^S.  Inputs tight; output tight (digit 1 may exceed 2^B by the last carry).
@@ -624,30 +675,36 @@ ECCX_DEV auto u_mul_add(const U<C, K1, V1>& a, const U<C, K2, V2>& b, const U<C,
 template <class C>
 struct UBS {
   static constexpr bool OK = UB<C>::SPARSE || C::KIND == UK_MONT;
+  // p = -1 mod 2^B with p + 1 as plain digits (P-256): the same budget, one product of tight limbs per side
+  static constexpr bool DENSE = C::KIND == UK_MONT_PP1 && !UB<C>::SPARSE;
   static constexpr int KKS = (int)((~(uint64_t)0 >> 1) / ((uint64_t)C::N * UB<C>::COL)) - 1;
+  // a negated (or doubled) operand limb below K * 2^B (+ a few units) fits a signed 32-bit register
+  static constexpr bool ks_ok(int k) { return ((uint64_t)(k + 1) << C::B) <= ((uint64_t)1 << 31); }
 };
 
-// a*b - c*d (+ p) with one reduction: sparse (P-384) and general (BLS12-381) Montgomery fields
+// a*b - c*d (+ p) with one reduction: sparse (P-384), dense (P-256) and general (BLS12-381) Montgomery fields
 template <class C, int K1, int V1, int K2, int V2, int K3, int V3, int K4, int V4>
 ECCX_DEV auto u_mul_sub(const U<C, K1, V1>& a, const U<C, K2, V2>& b, const U<C, K3, V3>& c, const U<C, K4, V4>& d) {
-  static_assert(UBS<C>::OK, "implemented for the Montgomery fields with room for signed columns");
+  static_assert(UBS<C>::OK || UBS<C>::DENSE, "implemented for the Montgomery fields with room for signed columns");
   static_assert(K1 * K2 <= UBS<C>::KKS && K3 * K4 <= UBS<C>::KKS, "a product overflows the signed columns");
-  static_assert(K3 <= 7 && K4 <= 7, "negated / signed operands must stay below 2^31");
+  static_assert(UBS<C>::ks_ok(K3) && UBS<C>::ks_ok(K4), "negated / signed operands must stay below 2^31");
   static_assert((uint32_t)(V1 * V2) < C::RP && (uint32_t)(V3 * V4) < C::RP, "result outside (0, 3p)");
   U<C, 1, 3> r;
   if constexpr (UB<C>::SPARSE) u_mul_sub_core_sparse<C, false>(r.v, a.v, b.v, c.v, d.v);
+  else if constexpr (UBS<C>::DENSE) u_mul_sub_core_pp1<C, false>(r.v, a.v, b.v, c.v, d.v);
   else u_mul_sub_core_mont<C, false>(r.v, a.v, b.v, c.v, d.v);
   return r;
 }
 // a*b - 2*c^2 (+ p) with one reduction
 template <class C, int K1, int V1, int K2, int V2, int K3, int V3>
 ECCX_DEV auto u_mul_sub_2sqr(const U<C, K1, V1>& a, const U<C, K2, V2>& b, const U<C, K3, V3>& c) {
-  static_assert(UBS<C>::OK, "implemented for the Montgomery fields with room for signed columns");
+  static_assert(UBS<C>::OK || UBS<C>::DENSE, "implemented for the Montgomery fields with room for signed columns");
   static_assert(K1 * K2 <= UBS<C>::KKS && 2 * K3 * K3 <= UBS<C>::KKS, "a product overflows the signed columns");
-  static_assert(2 * K3 <= 7, "doubled / negated operands must stay below 2^31");
+  static_assert(UBS<C>::ks_ok(2 * K3), "doubled / negated operands must stay below 2^31");
   static_assert((uint32_t)(V1 * V2) < C::RP && (uint32_t)(2 * V3 * V3) < C::RP, "result outside (0, 3p)");
   U<C, 1, 3> r;
   if constexpr (UB<C>::SPARSE) u_mul_sub_core_sparse<C, true>(r.v, a.v, b.v, c.v, c.v);
+  else if constexpr (UBS<C>::DENSE) u_mul_sub_core_pp1<C, true>(r.v, a.v, b.v, c.v, c.v);
   else u_mul_sub_core_mont<C, true>(r.v, a.v, b.v, c.v, c.v);
   return r;
 }
