@@ -52,6 +52,8 @@
 #pragma once
 #include "fe.hpp"
 
+#include <type_traits>
+
 #ifndef ECCX_SOLINAS_REDUCE
 #define ECCX_SOLINAS_REDUCE 1  // 0: A/B switch back to the generic signed 64-bit chain
 #endif
@@ -68,6 +70,23 @@ __device__ __forceinline__ void smad1_k(uint64_t& acc, uint32_t a, int32_t k) {
 // acc += a * b, both signed 32-bit register operands
 __device__ __forceinline__ void smad1_v(uint64_t& acc, int32_t a, int32_t b) {
   asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
+}
+
+// acc = hi32(acc) * 2^S: the carry out of a column whose Montgomery digit is its whole low word
+// (UB::LO32), one multiply-add in place of the mask and the 64-bit shift; signed for signed columns.  The
+// cores leave it pending in UMacQC::carry, which opens the next column's first chunk with it; these stand-alone
+// forms only serve a column without products
+template <int S>
+__device__ __forceinline__ void ucarry_hi(uint64_t& acc) {
+  uint64_t r;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=&v"(r) : "v"((uint32_t)(acc >> 32)), "n"(1 << S) : "vcc");
+  acc = r;
+}
+template <int S>
+__device__ __forceinline__ void scarry_hi(uint64_t& acc) {
+  uint64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, 0" : "=&v"(r) : "v"((uint32_t)(acc >> 32)), "n"(1 << S) : "vcc");
+  acc = r;
 }
 
 enum : int { UK_MONT_PP1 = 0, UK_MONT = 1, UK_MERSENNE = 2, UK_PM19 = 3 };
@@ -99,12 +118,39 @@ struct UB {
   // squares also shift the operand left by one (two for the wrapped cross terms)
   static constexpr int KSQ_SHIFT = WRAPPED ? 2 : 1;
   static constexpr bool ksq_ok(int k) { return k * k <= KKMAX && (k << KSQ_SHIFT) <= KMAX + 1; }
-  // bound of a product of values below v1*p and v2*p
+  // bound of a product of values below v1*p and v2*p (LO32: see below)
   static constexpr int vout(int v1, int v2) {
-    return MONT ? (int)(((uint32_t)(v1 * v2) + C::RP - 1) / C::RP) + 1 : (C::KIND == UK_PM19 ? 2 : 3);
+    return LO32   ? (int)((uint32_t)(v1 * v2) / C::RP) + 2
+           : MONT ? (int)(((uint32_t)(v1 * v2) + C::RP - 1) / C::RP) + 1
+                  : (C::KIND == UK_PM19 ? 2 : 3);
   }
   // laziest limb bound a value may have and still be squared / multiplied by a tight value
   static constexpr int KLAZY = ksq_ok(2) ? 2 : 1;
+
+  // p = -1 mod 2^B with p + 1 as plain digits (P-256): any m = acc mod 2^B is a valid Montgomery digit, so
+  // columns 0..N-2 take the whole low word m = lo32(acc) (no v_and), and acc - m = hi32(acc) * 2^32 carries
+  // into the next column as one multiply-add (no 64-bit shift).  Column N-1 keeps its masked digit.
+  static constexpr bool LO32 = C::KIND == UK_MONT_PP1 && !SPARSE;
+  static constexpr uint64_t pp1_sum() {
+    uint64_t s = 0;
+    for (int j = 0; j < C::N; ++j) s += C::PP1[j];
+    return s;
+  }
+  // column budget with 32-bit digits: N products of K1*K2 <= KKMAX, every non-zero digit of p + 1 times a
+  // digit below 2^32, the carry in (below 2^(64-B)); the reserve KKMAX keeps for the reduction is N*COL
+  static_assert(!LO32 || (uint64_t)C::N * KKMAX * COL <= ~(uint64_t)0 - 0xffffffffull * pp1_sum() -
+                                                          ((uint64_t)1 << (64 - C::B)),
+                "32-bit Montgomery digits overflow the columns");
+  // output: M = sum m_i 2^(B i) < R + E with E < 2^(33 + B(N-2)) (N-1 digits up to 2^32 in place of 2^B).
+  // (ab + M p) / R < (v1 v2 / RP + 1 + E/R) p, and E * RP <= R makes that at most (floor(v1 v2 / RP) + 2) p:
+  // the ceiling of vout() below, except where RP divides v1 v2, which gets one p more
+  static constexpr int log2_rp() {
+    int l = 0;
+    while (((uint32_t)2 << l) <= C::RP) ++l;
+    return l;
+  }
+  static_assert(!LO32 || 33 + C::B * (C::N - 2) + log2_rp() + 1 <= C::B * C::N,
+                "32-bit Montgomery digits: the excess of M over R must stay below R / RP");
 };
 
 // queue of pending single-instruction MACs (see MacQ in fe.hpp)
@@ -151,10 +197,68 @@ struct UMacQ {
   }
 };
 
+// the same queue for the cores with 32-bit Montgomery digits (UB::LO32): carry() leaves the column's carry h pending,
+// and the next flush starts from acc = h * 2^S inside the same asm statement (no wait state of its own)
+template <bool KC, int S>
+struct UMacQC {
+  UMacQ<KC> q;
+  int hc = 0;  // 0 none, 1 unsigned h, 2 signed h
+  uint32_t h;
+  ECCX_DEV void push(uint64_t& acc, uint32_t a, uint32_t b) {
+    q.x[q.n] = a;
+    q.y[q.n] = b;
+    if (++q.n == 9) flush(acc);
+  }
+  ECCX_DEV void carry(uint64_t acc, bool sgn) {
+    h = (uint32_t)(acc >> 32);
+    hc = sgn ? 2 : 1;
+  }
+  ECCX_DEV void flush(uint64_t& acc) {
+    if (hc) flush_carry(acc);
+    else q.flush(acc);
+  }
+  ECCX_DEV void flush_carry(uint64_t& acc) {
+    static_assert(S >= 1 && S <= 6, "carry factor 2^S must be an inline constant");
+    constexpr int F = 1 << S;
+#define ECCX_Q(i) q.x[i], q.y[i]
+#define ECCX_CHUNKS(SUF)                                                                                           \
+  switch (q.n) {                                                                                                     \
+    case 1: umad1_##SUF<F>(acc, h, ECCX_Q(0)); break;                                                              \
+    case 2: umad2_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1)); break;                                                   \
+    case 3: umad3_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2)); break;                                        \
+    case 4: umad4_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3)); break;                             \
+    case 5: umad5_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4)); break;                  \
+    case 6: umad6_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5)); break;       \
+    case 7: umad7_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6));   \
+      break;                                                                                                       \
+    case 8:                                                                                                        \
+      umad8_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6), ECCX_Q(7)); \
+      break;                                                                                                       \
+    case 9:                                                                                                        \
+      umad9_##SUF<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6), ECCX_Q(7), \
+                     ECCX_Q(8));                                                                                   \
+      break;                                                                                                       \
+    default:                                                                                                       \
+      if (hc == 2) scarry_hi<S>(acc);                                                                              \
+      else ucarry_hi<S>(acc);                                                                                      \
+      break;                                                                                                       \
+  }
+    if constexpr (KC) {
+      if (hc == 2) { ECCX_CHUNKS(ks) } else { ECCX_CHUNKS(kc) }
+    } else {
+      if (hc == 2) { ECCX_CHUNKS(vs) } else { ECCX_CHUNKS(vc) }
+    }
+#undef ECCX_CHUNKS
+#undef ECCX_Q
+    q.n = 0;
+    hc = 0;
+  }
+};
+
 // ---- product cores on raw limb arrays; bounds are checked by the typed wrappers -----------
 
 // Montgomery product / square (kinds 0 and 1): product scanning, one 64-bit column at a time
-template <class C, bool SQR, bool BCONST>
+template <class C, bool SQR, bool BCONST, bool LO32 = UB<C>::LO32>
 ECCX_DEV void u_mul_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N]) {
   constexpr int N = C::N;
   constexpr bool PP1 = C::KIND == UK_MONT_PP1;
@@ -166,7 +270,7 @@ ECCX_DEV void u_mul_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], co
     for (int i = 0; i < N; ++i) a2[i] = a[i] << 1;
   }
   uint64_t acc = 0;
-  UMacQ<BCONST> qa;
+  std::conditional_t<UB<C>::LO32, UMacQC<BCONST, 32 - C::B>, UMacQ<BCONST>> qa;
   UMacQ<true> qm;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; ++k) {
@@ -203,6 +307,14 @@ ECCX_DEV void u_mul_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], co
         if (PR(k - i) != 0) qm.push(acc, m[i], PR(k - i));
       }
       qm.flush(acc);
+    }
+    if constexpr (LO32) {
+      if (k < N - 1) {
+        // m[k] = the whole low word (UB::LO32): "- m" leaves hi32(acc) * 2^32, i.e. hi32(acc) * 2^(32-B) above
+        m[k] = (uint32_t)acc;
+        qa.carry(acc, false);
+        continue;
+      }
     }
     if (k < N) {
       if constexpr (PP1) {
@@ -381,12 +493,14 @@ ECCX_DEV void u_mul_sub_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N]
 
 // The same for p = -1 mod 2^B without the sparse form (P-256): m*(p+1) enters as its non-zero digits, as in
 // u_mul_core_mont, on columns read as signed.  Column bound, either side below 2^63 = 32 * 2^(2B) for B = 29:
-//   positive  a*b: at most N = 9 products below K1*K2 * 2^(2B) (K1*K2 <= UBS::KKS = 2: 18 * 2^(2B)); m*(p+1): at
-//             most 4 products below 2^(2B) (digits 3, 6, 7, 8 of p + 1); a digit of p (< 2^B); carry in < 2^(63-B)
-//             -> below 22 * 2^(2B) + 2^35
+//   positive  a*b: at most N = 9 products below K1*K2 * 2^(2B) (K1*K2 <= UBS::KKS = 2: 18 * 2^(2B)); m*(p+1): the
+//             4 non-zero digits of p + 1 (3, 6, 7, 8; sum < 2^29.04) times digits below 2^32 (< 8.23 * 2^(2B)); a
+//             digit of p (< 2^B); carry in < 2^(63-B) -> below 26.3 * 2^(2B) + 2^35
 //   negative  c*d (or 2 c^2): at most 9 products below K3*K4 * 2^(2B) (or 2 K3^2 <= KKS: 18 * 2^(2B)); carry in
 //             above -2^(63-B)
-// and the low limb is taken as the Montgomery factor (-p^-1 mod 2^B = 1) exactly as in the unsigned core.
+// and the low word is taken as the Montgomery factor (-p^-1 mod 2^B = 1) exactly as in the unsigned core (32-bit
+// digits in columns 0..N-2, UB::LO32; the static_assert in UBS checks this budget).  With M < R (1 + 2^-26) the
+// result stays in (0, 3p): V1*V2 <= RP - 1 leaves (1 - 1/RP) p for the excess.
 template <class C, bool NEG_SQ>
 ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N],
                                  const uint32_t (&c)[C::N], const uint32_t (&d)[C::N]) {
@@ -397,7 +511,7 @@ ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N],
 #pragma unroll
   for (int i = 0; i < N; ++i) nc[i] = NEG_SQ ? -(int32_t)(c[i] << 1) : -(int32_t)c[i];
   uint64_t acc = 0;
-  UMacQ<false> qa;
+  UMacQC<false, 32 - C::B> qa;
   UMacQ<true> qm;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; ++k) {
@@ -419,6 +533,12 @@ ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N],
       if (C::PP1[k - i] != 0) qm.push(acc, m[i], C::PP1[k - i]);
     }
     qm.flush(acc);
+    if (k < N - 1) {
+      // 32-bit digit as in u_mul_core_mont (UB::LO32); hi32(acc) is signed here
+      m[k] = (uint32_t)acc;
+      qa.carry(acc, true);
+      continue;
+    }
     if (k < N) m[k] = (uint32_t)acc & C::MASK;
     else t[k - N] = (uint32_t)acc & C::MASK;
     acc = (uint64_t)((int64_t)acc >> C::B);
@@ -678,6 +798,11 @@ struct UBS {
   // p = -1 mod 2^B with p + 1 as plain digits (P-256): the same budget, one product of tight limbs per side
   static constexpr bool DENSE = C::KIND == UK_MONT_PP1 && !UB<C>::SPARSE;
   static constexpr int KKS = (int)((~(uint64_t)0 >> 1) / ((uint64_t)C::N * UB<C>::COL)) - 1;
+  // DENSE takes 32-bit digits too (UB::LO32): the positive side of a column, N products of K1*K2 <= KKS, the
+  // non-zero digits of p + 1 times digits below 2^32, a digit of p and the carry in, stays below 2^63
+  static_assert(!DENSE || (uint64_t)C::N * KKS * UB<C>::COL <= (~(uint64_t)0 >> 1) - 0xffffffffull * UB<C>::pp1_sum() -
+                                                                ((uint64_t)1 << C::B) - ((uint64_t)1 << (63 - C::B)),
+                "32-bit Montgomery digits overflow the signed columns");
   // a negated (or doubled) operand limb below K * 2^B (+ a few units) fits a signed 32-bit register
   static constexpr bool ks_ok(int k) { return ((uint64_t)(k + 1) << C::B) <= ((uint64_t)1 << 31); }
 };
@@ -730,6 +855,17 @@ ECCX_DEV auto u_mul_k(const U<C, K1, V1>& a, const uint32_t (&k)[C::N]) {
     u_mul_core<C, false, true>(r.v, a.v, k);
     return r;
   }
+}
+
+// a * k / R for the exits to saturated limbs (u_to_canonical, u_to_sat_mont), whose bounds need M < R: the masked
+// Montgomery digits.  With 32-bit digits (UB::LO32) M may exceed R by R * 2^-26, and so the result p by p * 2^-26:
+// past 2^256 for P-256, where p + (2^256 mod p) = 2^256 would lose its top bit in 8 saturated words.
+template <class C>
+ECCX_DEV U<C, 1, 2> u_mul_k_exit(const U<C, 1, 3>& a, const uint32_t (&k)[C::N]) {
+  static_assert(UB<C>::MONT && UB<C>::vout(3, 1) <= 2, "Montgomery fields; a reduced operand times a constant below p");
+  U<C, 1, 2> r;
+  u_mul_core_mont<C, false, true, false>(r.v, a.v, k);
+  return r;
 }
 
 // multiply by a small constant k < 2^20 (kind 3 only: the ladder's (A + 2) / 4): one mad per limb
@@ -951,7 +1087,7 @@ ECCX_DEV void u_to_canonical(Fe<C::Sat::L>& out, const U<C, K, V>& a) {
 #pragma unroll
     for (int i = 0; i < C::N; ++i) one[i] = (i == 0) ? 1u : 0u;
     // (a + m p) / R with a < 3p << R: the result is in [0, p]
-    auto r = u_mul_k<C>(u_reduce(a), one);
+    auto r = u_mul_k_exit<C>(u_reduce(a), one);
     u_to_sat<C>(s, r);
   } else {
     // twice: the second pass sees exact digits, so its quotient is exact and the result <= p + 2
@@ -970,7 +1106,7 @@ template <class C, int K, int V>
 ECCX_DEV void u_to_sat_mont(Fe<C::Sat::L>& out, const U<C, K, V>& a) {
   if constexpr (UB<C>::MONT) {
     // (a * R_sat + m p) / R with a < 3p, R_sat < p: below p (1 + 3p/R), one conditional subtraction
-    auto r = u_mul_k<C>(u_reduce(a), C::RS);
+    auto r = u_mul_k_exit<C>(u_reduce(a), C::RS);
     Fe<C::Sat::L> s;
     u_to_sat<C>(s, r);
     uint32_t t[C::Sat::L];
