@@ -72,6 +72,9 @@ struct eccx_ctx {
   // which the host-buffer form fills with its copies
   uint8_t* ecdsa = nullptr;
   size_t ecdsa_cap = 0;
+  // the same for eccx_ed25519_verify_dev (u1, u2, decoded keys, the ladder's x || y and flags)
+  uint8_t* ed = nullptr;
+  size_t ed_cap = 0;
   static constexpr int NEV = 10;
   hipEvent_t evs[NEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::mutex err_mu;       // err is written by whichever host thread's call failed last
@@ -166,28 +169,46 @@ size_t ecdsa_slab_bytes(const CurveOps* ops, size_t n) {
   const size_t sb = (size_t)ops->info.sb, fb = (size_t)ops->info.fb;
   return 2 * align16(n * sb) + align16(n * fb) + align16(n) + n * 2 * fb;
 }
-int ensure_ecdsa(eccx_ctx* ctx, const CurveOps* ops, size_t n, EcdsaSlab* out) {
-  const size_t bytes = ecdsa_slab_bytes(ops, n);
-  {
-    std::lock_guard<std::mutex> g(ctx->scratch_mu);
-    if (bytes > ctx->ecdsa_cap) {
-      if (ctx->ecdsa) {
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipFree(ctx->ecdsa));
-        ctx->ecdsa = nullptr;
-        ctx->ecdsa_cap = 0;
-      }
-      HIP_TRY(ctx, hipMalloc(&ctx->ecdsa, bytes));
-      ctx->ecdsa_cap = bytes;
+// grow-only working slab of a verification entry point
+int grow_slab(eccx_ctx* ctx, uint8_t** buf, size_t* cap, size_t bytes) {
+  std::lock_guard<std::mutex> g(ctx->scratch_mu);
+  if (bytes > *cap) {
+    if (*buf) {
+      HIP_TRY(ctx, hipDeviceSynchronize());
+      HIP_TRY(ctx, hipFree(*buf));
+      *buf = nullptr;
+      *cap = 0;
     }
+    HIP_TRY(ctx, hipMalloc(buf, bytes));
+    *cap = bytes;
   }
-  if (!out) return ECCX_OK;
+  return ECCX_OK;
+}
+int ensure_ecdsa(eccx_ctx* ctx, const CurveOps* ops, size_t n, EcdsaSlab* out) {
+  const int rc = grow_slab(ctx, &ctx->ecdsa, &ctx->ecdsa_cap, ecdsa_slab_bytes(ops, n));
+  if (rc || !out) return rc;
   const size_t sb = (size_t)ops->info.sb, fb = (size_t)ops->info.fb;
   out->u1 = ctx->ecdsa;
   out->u2 = out->u1 + align16(n * sb);
   out->x = out->u2 + align16(n * sb);
   out->lflags = out->x + align16(n * fb);
   out->keys = out->lflags + align16(n);
+  return ECCX_OK;
+}
+
+// the Ed25519 slab: u1, u2 (n x 32), the ladder's flags (n), decoded keys and the ladder's x || y (n x 64 each)
+struct EdSlab {
+  uint8_t *u1, *u2, *lflags, *keys, *pts;
+};
+size_t ed_slab_bytes(size_t n) { return 2 * align16(n * 32) + align16(n) + align16(n * 64) + n * 64; }
+int ensure_ed(eccx_ctx* ctx, size_t n, EdSlab* out) {
+  const int rc = grow_slab(ctx, &ctx->ed, &ctx->ed_cap, ed_slab_bytes(n));
+  if (rc || !out) return rc;
+  out->u1 = ctx->ed;
+  out->u2 = out->u1 + align16(n * 32);
+  out->lflags = out->u2 + align16(n * 32);
+  out->keys = out->lflags + align16(n);
+  out->pts = out->keys + align16(n * 64);
   return ECCX_OK;
 }
 
@@ -504,9 +525,11 @@ struct HostOut { uint8_t* host; const uint8_t* dev; size_t width; };
 // public-scalar fixed-base kernels are shorter than their copies and lose to the per-chunk launch costs, 3.4 ->
 // 4.5 ms; the secret-scalar combs take the chunks, 5.3 -> 4.3 ms).  launch(lo, cnt) enqueues the kernels of units
 // lo .. lo + cnt on ctx->stream and returns an ECCX code.
-template <class Launch>
-int host_pipeline(eccx_ctx* ctx, size_t n, const HostIn* ins, int nins, const HostOut* outs, int nouts, bool chunked,
-                  Launch launch) {
+// copy_in(lo, cnt, stream) enqueues copies of a chunk's inputs that are no fixed-width records (Ed25519's messages) on
+// the copy stream and returns a hipError_t.
+template <class Launch, class CopyIn>
+int host_pipeline_x(eccx_ctx* ctx, size_t n, const HostIn* ins, int nins, const HostOut* outs, int nouts, bool chunked,
+                    Launch launch, CopyIn copy_in) {
   const size_t nchunks = (chunked && n >= ((size_t)1 << 17)) ? 4 : 1;
   static_assert(2 * 4 <= eccx_ctx::NEV, "two events per chunk");
   const size_t step = ((n + nchunks - 1) / nchunks + 4095) / 4096 * 4096;
@@ -544,6 +567,7 @@ int host_pipeline(eccx_ctx* ctx, size_t n, const HostIn* ins, int nins, const Ho
       if (ins[i].host)
         TRY2_(hipMemcpyAsync(ins[i].dev + lo * ins[i].width, ins[i].host + lo * ins[i].width, cnt * ins[i].width,
                              hipMemcpyHostToDevice, s_in));
+    TRY2_(copy_in(lo, cnt, s_in));
     hipEvent_t done = nullptr;
     if (nchunks > 1) {
       hipEvent_t in_ready = ctx->evs[next_ev++];
@@ -564,6 +588,11 @@ int host_pipeline(eccx_ctx* ctx, size_t n, const HostIn* ins, int nins, const Ho
   if (s_out != ctx->stream) TRY2_(hipStreamSynchronize(ctx->stream));
 #undef TRY2_
   return ECCX_OK;
+}
+template <class Launch>
+int host_pipeline(eccx_ctx* ctx, size_t n, const HostIn* ins, int nins, const HostOut* outs, int nouts, bool chunked,
+                  Launch launch) {
+  return host_pipeline_x(ctx, n, ins, nins, outs, nouts, chunked, launch, [](size_t, size_t, hipStream_t) { return hipSuccess; });
 }
 
 // host-buffer wrapper shared by var / base
@@ -716,6 +745,7 @@ void eccx_shutdown(eccx_ctx* ctx) {
   for (auto& b : ctx->io)
     if (b) (void)hipFree(b);
   if (ctx->ecdsa) (void)hipFree(ctx->ecdsa);
+  if (ctx->ed) (void)hipFree(ctx->ed);
   for (auto& e : ctx->evs)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -772,7 +802,7 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc = ensure_rows(ctx, ops, max_n);  // every entry point writes un-normalised rows first
   if (rc) return rc;
-  if (what & (ECCX_PREP_VAR | ECCX_PREP_ECDSA)) {  // window-table slab of the default ladder (also the fused double-scalar kernel)
+  if (what & (ECCX_PREP_VAR | ECCX_PREP_ECDSA | ECCX_PREP_ED25519)) {  // window-table slab of the default ladder (also the fused double-scalar kernel)
     const int grid = ops->var_fast_grid ? ops->var_fast_grid(ctx->cus, max_n) : grid_for(ctx, max_n);
     rc = ensure_scratch(ctx, ops->info.row5_words, grid);
     if (rc) return rc;
@@ -813,6 +843,10 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     rc = ensure_ecdsa(ctx, ops, max_n, nullptr);
     if (rc) return rc;
   }
+  if ((what & ECCX_PREP_ED25519) && ops->ed_verify_prepare) {  // eccx_ed25519_verify's
+    rc = ensure_ed(ctx, max_n, nullptr);
+    if (rc) return rc;
+  }
   // slab of the reference-mirroring ladder (also what ECCX_CT_SCAN runs on a curve without a scanning fast ladder)
   const bool mirror_slab = (what & ECCX_PREP_MIRROR) || ((what & ECCX_PREP_CT) && !ops->var_ct);
   if (mirror_slab && ops->info.row_words) {
@@ -830,7 +864,7 @@ size_t eccx_device_bytes(const eccx_ctx* ctx) {
   std::lock_guard<std::mutex> g2(c->scratch_mu);
   size_t io = 0;
   for (size_t b : c->io_cap) io += b;
-  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap;
+  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap + c->ed_cap;
 }
 
 int eccx_scalarmul_var_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points,
@@ -1194,6 +1228,71 @@ int eccx_ecdsa_verify(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests
     return eccx_ecdsa_verify_dev(ctx, curve, cnt, d_d + lo * db, digest_bytes, d_s + lo * 2 * sb, d_k + lo * kb, d_v + lo, opts,
                                  ctx->stream);
   });
+}
+
+int eccx_ed25519_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_sigs,
+                            const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts != 0) return arg_err(ctx, "eccx_ed25519_verify: opts must be 0");
+  if (n == 0) return ECCX_OK;
+  if (!d_msgs || !d_offsets || !d_sigs || !d_pubkeys || !d_verdicts) return arg_err(ctx, "null buffer");
+  const CurveOps* ops = ops_of(ECCX_ED25519);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EdSlab w;
+  int rc = ensure_ed(ctx, n, &w);
+  if (rc) return rc;
+  const uint8_t* sigs = static_cast<const uint8_t*>(d_sigs);
+  uint8_t* verdicts = static_cast<uint8_t*>(d_verdicts);
+  // A decoded into the slab; the decoder's flags park in the verdicts until the next pass
+  HIP_TRY(ctx, ops->decompress(flat_grid(ctx, n), s, n, static_cast<const uint8_t*>(d_pubkeys), w.keys, verdicts));
+  HIP_TRY(ctx, ops->ed_verify_prepare(flat_grid(ctx, n), s, n, static_cast<const uint8_t*>(d_msgs),
+                                      static_cast<const uint64_t*>(d_offsets), sigs, static_cast<const uint8_t*>(d_pubkeys),
+                                      verdicts, w.u1, w.u2, verdicts));
+  // [S]B - [k]A; rejected keys were decoded as (0, 0) and their lanes' results are not read
+  rc = verify_shape(ctx, ECCX_ED25519, ops, n, w.u1, w.u2, w.keys, w.pts, w.lflags, ECCX_SUBTRACT, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, ops->ed_verify_finish(flat_grid(ctx, n), s, n, sigs, w.pts, verdicts));
+  return ECCX_OK;
+}
+
+int eccx_ed25519_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* sigs,
+                        const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts != 0) return arg_err(ctx, "eccx_ed25519_verify: opts must be 0");
+  if (n == 0) return ECCX_OK;
+  if (!offsets || !sigs || !pubkeys || !verdicts) return arg_err(ctx, "null buffer");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return arg_err(ctx, "eccx_ed25519_verify: the offsets decrease");
+  const size_t total = (size_t)(offsets[n] - offsets[0]);
+  if (total && !msgs) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t *d_m = nullptr, *d_o = nullptr, *d_s = nullptr, *d_k = nullptr, *d_v = nullptr;
+  int rc = ensure_io(ctx, IO_J, total ? total : 1, &d_m);
+  if (!rc) rc = ensure_io(ctx, IO_K, (n + 1) * sizeof(uint64_t), &d_o);
+  if (!rc) rc = ensure_io(ctx, IO_O, n * 64, &d_s);
+  if (!rc) rc = ensure_io(ctx, IO_P, n * 32, &d_k);
+  if (!rc) rc = ensure_io(ctx, IO_F, n, &d_v);
+  if (rc) return rc;
+  const HostIn ins[2] = {{d_s, sigs, 64}, {d_k, pubkeys, 32}};
+  const HostOut outs[1] = {{verdicts, d_v, 1}};
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_o);
+  // a chunk of signatures lo .. lo + cnt is a batch of its own: offsets[lo .. lo + cnt] and the message bytes they span,
+  // kept at the same places on the device as on the host
+  return host_pipeline_x(
+      ctx, n, ins, 2, outs, 1, /*chunked=*/true,
+      [&](size_t lo, size_t cnt) {
+        return eccx_ed25519_verify_dev(ctx, cnt, d_m + (offsets[lo] - offsets[0]), d_off + lo, d_s + lo * 64, d_k + lo * 32,
+                                       d_v + lo, 0, ctx->stream);
+      },
+      [&](size_t lo, size_t cnt, hipStream_t st) {
+        const size_t first = lo == 0 ? 0 : lo + 1;  // offsets[lo] came with the chunk before
+        hipError_t e = hipMemcpyAsync(d_o + first * sizeof(uint64_t), offsets + first, (lo + cnt + 1 - first) * sizeof(uint64_t),
+                                      hipMemcpyHostToDevice, st);
+        const size_t a = (size_t)(offsets[lo] - offsets[0]), b = (size_t)(offsets[lo + cnt] - offsets[0]);
+        if (e == hipSuccess && b > a) e = hipMemcpyAsync(d_m + a, msgs + a, b - a, hipMemcpyHostToDevice, st);
+        return e;
+      });
 }
 
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,

@@ -1,6 +1,7 @@
 // Kernel instantiations for edwards25519 (see kernels.hpp).
 #include "kernels_codec.hpp"
 #include "kernels_ct.hpp"
+#include "kernels_ed25519_verify.hpp"
 #include "launch.hpp"
 
 namespace eccx {
@@ -119,6 +120,17 @@ hipError_t base_ctg_(int grid, hipStream_t s, size_t n, const uint8_t* scalars, 
   hipLaunchKernelGGL((k_ed_scalarmul_base_ct<ED25519U, true>), dim3(grid), dim3(WG), 0, s, n, scalars, table, rows, flags);
   return hipGetLastError();
 }
+// Ed25519 verification (kernels_ed25519_verify.hpp): the passes before and after the verify shape
+hipError_t ed_verify_prepare_(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* sigs,
+                              const uint8_t* pubkeys, const uint8_t* key_flags, uint8_t* u1, uint8_t* u2, uint8_t* verdicts) {
+  hipLaunchKernelGGL((k_ed_verify_prepare<ED25519, ED25519_ORD>), dim3(grid), dim3(WG), 0, s, n, msgs, offsets, sigs, pubkeys, key_flags,
+                     u1, u2, verdicts);
+  return hipGetLastError();
+}
+hipError_t ed_verify_finish_(int grid, hipStream_t s, size_t n, const uint8_t* sigs, const uint8_t* pts, uint8_t* verdicts) {
+  hipLaunchKernelGGL(k_ed_verify_finish<ED25519U>, dim3(grid), dim3(WG), 0, s, n, sigs, pts, verdicts);
+  return hipGetLastError();
+}
 }  // namespace
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u, uint32_t* rows,
                                 uint8_t* flags, uint32_t opts) {
@@ -147,6 +159,8 @@ const CurveOps& ops_ED25519() {
     t.base_ctg = base_ctg_;
     t.var_ct = var_ct_;
     t.var_ct_grid = var_ct_grid_;
+    t.ed_verify_prepare = ed_verify_prepare_;
+    t.ed_verify_finish = ed_verify_finish_;
     return t;
   }();
   return o;

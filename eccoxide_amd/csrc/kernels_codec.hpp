@@ -311,8 +311,38 @@ __global__ void __launch_bounds__(WG) k_point_from_uncompressed(size_t n, const 
 }
 
 // edwards25519, RFC 8032 (protocol/ed25519.rs:38-59 decode_point, curve25519.rs:772-784
-// decompress, :246-265 sqrt_div): flags 0 point, 2 rejected (y not below p, x = 0 with the sign
-// bit set, (y^2 - 1) / (d y^2 + 1) not a square).  out = x||y little-endian.
+// decompress, :246-265 sqrt_div), the part both users share: from the 32 bytes at e, declares
+// ry (y, sign bit cleared), want (the sign bit: low bit of x), status (CODEC_INVALID for y not
+// below p, x = 0 with the sign bit set, (y^2 - 1) / (d y^2 + 1) not a square) and r (a root:
+// x or -x).  Users: k_ed_point_decompress and Ed25519 verification's test of R
+// (kernels_ed25519_verify.hpp).  A macro rather than a function so that the decoder kernel is
+// compiled from the statements it always had: behind a function boundary hipcc orders the operands
+// of a few hundred commutative adds differently.
+#define ECCX_ED_DECODE(CU, e)                                                                                     \
+  using CS_ = typename CU::Sat;                                                                                    \
+  Fe<CS_::L> ry;                                                                                                   \
+  fe_load_le<CS_>(ry, e);                                                                                          \
+  const bool want = (ry.v[CS_::L - 1] >> 31) != 0; /* low bit of x */                                              \
+  ry.v[CS_::L - 1] &= 0x7FFFFFFFu;                                                                                 \
+  uint8_t status = fe_is_canonical<CS_>(ry) ? CODEC_OK : CODEC_INVALID;                                            \
+  UT<CU> one, d, im;                                                                                               \
+  _Pragma("unroll") for (int k = 0; k < CU::N; ++k) { one.v[k] = CU::ONE[k]; d.v[k] = CU::D[k]; im.v[k] = CU::SQRT_M1[k]; } \
+  const UT<CU> y = u_as<1, 3>(u_from_sat<CU>(ry));                                                                 \
+  const UT<CU> yy = u_fit<1, 3>(u_sqr(y));                                                                         \
+  const UT<CU> u = u_fit<1, 3>(u_reduce(u_sub(yy, one)));                                                          \
+  const UT<CU> v = u_fit<1, 3>(u_reduce(u_add(ut_mul(d, yy), one)));                                              \
+  /* x = 0 exactly for y = +-1, i.e. u = 0: that encoding must have a clear sign bit */                            \
+  if (want && u_is_zero_mod_p(u)) status = CODEC_INVALID;                                                          \
+  const UT<CU> v3 = ut_mul(u_sqr(v), v);                                                                           \
+  const UT<CU> v7 = ut_mul(u_sqr(v3), v);                                                                          \
+  UT<CU> r = ut_mul(ut_mul(u, v3), ut_root_pow<CU>(ut_mul(u, v7)));                                                \
+  const UT<CU> check = ut_mul(v, u_sqr(r));                                                                        \
+  const bool correct = ut_equal(check, u);                                                                         \
+  const bool flipped = u_is_zero_mod_p(u_reduce(u_add(check, u)));                                                \
+  if (flipped) r = ut_mul(r, im); /* v r^2 = -u: i r is the root */                                                \
+  if (!(correct || flipped)) status = CODEC_INVALID
+
+// flags 0 point, 2 rejected.  out = x||y little-endian.
 template <class CU>
 __global__ void __launch_bounds__(WG) k_ed_point_decompress(size_t n, const uint8_t* __restrict__ enc, uint8_t* __restrict__ out,
                                                             uint8_t* __restrict__ flags) {
@@ -321,28 +351,7 @@ __global__ void __launch_bounds__(WG) k_ed_point_decompress(size_t n, const uint
   static_assert(CU::KIND == UK_PM19 && L == 8, "written for 2^255 - 19");
   for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG) {
     const uint8_t* __restrict__ e = enc + i * 32;
-    Fe<L> ry;
-    fe_load_le<CS>(ry, e);
-    const bool want = (ry.v[L - 1] >> 31) != 0;  // low bit of x
-    ry.v[L - 1] &= 0x7FFFFFFFu;
-    uint8_t status = fe_is_canonical<CS>(ry) ? CODEC_OK : CODEC_INVALID;
-    UT<CU> one, d, im;
-#pragma unroll
-    for (int k = 0; k < CU::N; ++k) { one.v[k] = CU::ONE[k]; d.v[k] = CU::D[k]; im.v[k] = CU::SQRT_M1[k]; }
-    const UT<CU> y = u_as<1, 3>(u_from_sat<CU>(ry));
-    const UT<CU> yy = u_fit<1, 3>(u_sqr(y));
-    const UT<CU> u = u_fit<1, 3>(u_reduce(u_sub(yy, one)));
-    const UT<CU> v = u_fit<1, 3>(u_reduce(u_add(ut_mul(d, yy), one)));
-    // x = 0 exactly for y = +-1, i.e. u = 0: that encoding must have a clear sign bit
-    if (want && u_is_zero_mod_p(u)) status = CODEC_INVALID;
-    const UT<CU> v3 = ut_mul(u_sqr(v), v);
-    const UT<CU> v7 = ut_mul(u_sqr(v3), v);
-    UT<CU> r = ut_mul(ut_mul(u, v3), ut_root_pow<CU>(ut_mul(u, v7)));
-    const UT<CU> check = ut_mul(v, u_sqr(r));
-    const bool correct = ut_equal(check, u);
-    const bool flipped = u_is_zero_mod_p(u_reduce(u_add(check, u)));
-    if (flipped) r = ut_mul(r, im);  // v r^2 = -u: i r is the root
-    if (!(correct || flipped)) status = CODEC_INVALID;
+    ECCX_ED_DECODE(CU, e);
     Fe<L> x, xn;
     u_to_canonical<CU>(x, r);
     fe_neg_canonical<CS>(xn, x);

@@ -132,6 +132,13 @@ struct CurveOps {
                               const uint8_t* key_flags, uint8_t* u1, uint8_t* u2, uint8_t* verdicts);
   hipError_t (*ecdsa_finish)(int grid, hipStream_t s, size_t n, const uint8_t* sigs, const uint8_t* xs, const uint8_t* lflags,
                              uint8_t* verdicts);
+  // Ed25519 verification (kernels_ed25519_verify.hpp; edwards25519 only): ed_verify_prepare checks S and R's bytes,
+  // hashes R || A || M and writes u1 = S, u2 = k (32 bytes each, big-endian) and the pre-verdicts; key_flags (may alias
+  // verdicts) are A's decoder flags.  ed_verify_finish compares the encoding of the verify shape's affine x || y with R.
+  hipError_t (*ed_verify_prepare)(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets,
+                                  const uint8_t* sigs, const uint8_t* pubkeys, const uint8_t* key_flags, uint8_t* u1, uint8_t* u2,
+                                  uint8_t* verdicts);
+  hipError_t (*ed_verify_finish)(int grid, hipStream_t s, size_t n, const uint8_t* sigs, const uint8_t* pts, uint8_t* verdicts);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above

@@ -29,8 +29,9 @@ OUT_X_ONLY = 1 << 11
 PUBKEY_SEC1 = 1 << 12
 PREP_VAR, PREP_BASE, PREP_BASE_LDS, PREP_MIRROR, PREP_CT, PREP_CT_GATHER, PREP_HOST = 1, 2, 4, 8, 16, 32, 64
 PREP_ECDSA = 128
+PREP_ED25519 = 256
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
-# ECDSA verdicts (include/eccx.h: ECCX_SIG_*)
+# ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
 SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
 ECDSA_CURVES = (P256R1, P384R1, P521R1, P256K1)
 
@@ -140,13 +141,14 @@ class Engine:
                                            | (PREP_CT if ct else 0) | (PREP_CT_GATHER if ct_gather else 0)))
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
-                ecdsa: bool = False):
+                ecdsa: bool = False, ed25519: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
-        secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify."""
+        secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
+        ed25519_verify (curve "ed25519")."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
-                                           | (PREP_ECDSA if ecdsa else 0)))
+                                           | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -285,6 +287,56 @@ class Engine:
         self._check(self._lib.eccx_ecdsa_verify_dev(self._ctx, cid, n, digests.data_ptr(), db, sigs.data_ptr(),
                                                     pubkeys.data_ptr(), verdicts.data_ptr(), PUBKEY_SEC1 if sec1 else 0,
                                                     stream))
+        return verdicts
+
+    def ed25519_verify(self, messages, sigs: bytes, pubkeys: bytes) -> bytes:
+        """Ed25519 verification of a batch (eccx_ed25519_verify; src/protocol/ed25519.rs verify): messages is a list of
+        n byte strings, sigs n x 64 R || S, pubkeys n x 32 RFC 8032 encodings.  Returns n verdict bytes (SIG_*)."""
+        import numpy as np
+
+        n = len(messages)
+        if len(sigs) != 64 * n or len(pubkeys) != 32 * n:
+            raise ValueError("sigs must be n x 64 bytes and pubkeys n x 32 bytes for n messages")
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(m) for m in messages], out=offsets[1:])
+        msgs = b"".join(bytes(m) for m in messages)
+        verdicts = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_ed25519_verify(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, sigs, pubkeys,
+                                                  verdicts, 0))
+        return verdicts.raw[:n]
+
+    def ed25519_verify_t(self, msgs, offsets, sigs, pubkeys, verdicts=None, *, stream: Optional[int] = None,
+                         check_bounds: bool = True):
+        """Device-tensor form of ed25519_verify (eccx_ed25519_verify_dev): msgs the concatenated messages (torch.uint8),
+        offsets n + 1 int64 (message i is msgs[offsets[i] - offsets[0] : offsets[i + 1] - offsets[0]]), sigs n x 64,
+        pubkeys n x 32, all CUDA tensors.  Enqueued on `stream` (default: torch's current stream); returns the n-byte
+        verdict tensor.  A lane whose offsets decrease is SIG_MALFORMED.  check_bounds (default) reads the offsets'
+        extremes back on `stream` (a synchronisation) and refuses offsets that are negative or span more than msgs: the
+        kernels cannot check that themselves."""
+        import torch
+
+        n = self._units(sigs, 64, "sigs")
+        if offsets.dtype not in (torch.int64, torch.uint64) or offsets.numel() != n + 1 or not offsets.is_contiguous():
+            raise ValueError(f"offsets must be a contiguous int64 tensor of n + 1 = {n + 1} entries")
+        if not offsets.is_cuda or not msgs.is_cuda or msgs.dtype != torch.uint8 or not msgs.is_contiguous():
+            raise ValueError("msgs (contiguous uint8) and offsets must be CUDA tensors")
+        if verdicts is None:
+            verdicts = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
+        self._tensors(n, ("sigs", sigs, 64), ("pubkeys", pubkeys, 32), ("verdicts", verdicts, 1))
+        for name, t in (("msgs", msgs), ("offsets", offsets)):
+            if t.device.index != self.device:
+                raise ValueError(f"{name}: tensor lives on cuda:{t.device.index}, this engine is bound to cuda:{self.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(sigs.device).cuda_stream
+        if check_bounds and n:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=sigs.device)):
+                lo, hi, first = (int(v) for v in torch.stack([offsets.min(), offsets.max(), offsets[0]]).cpu())
+            if lo < 0 or hi - first > msgs.numel():
+                raise ValueError(f"offsets span {hi - first} bytes from offsets[0] (min {lo}); msgs holds {msgs.numel()}")
+        if msgs.numel() == 0:  # every message empty: any valid address
+            msgs = torch.zeros((1,), dtype=torch.uint8, device=sigs.device)
+        self._check(self._lib.eccx_ed25519_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), sigs.data_ptr(),
+                                                      pubkeys.data_ptr(), verdicts.data_ptr(), 0, stream))
         return verdicts
 
     def compressed_bytes(self, curve) -> int:

@@ -20,6 +20,7 @@
  *   eccx_point_add[_dev]       impl Add / Sub / Neg, CurveGroup::double   curve_macros.rs:297-411, group.rs:28-70
  *   eccx_double_scalarmul[_dev]  u1*G + u2*Q                     src/protocol/ecdsa.rs:215, ed25519.rs:145
  *   eccx_ecdsa_verify[_dev]      ECDSA verification              src/protocol/ecdsa.rs:200-222
+ *   eccx_ed25519_verify[_dev]    Ed25519 verification            src/protocol/ed25519.rs:119-146
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
@@ -192,6 +193,8 @@ enum {
   ECCX_PREP_HOST = 1u << 6,     /* eccx_reserve: the device-side copies the HOST-buffer entry points keep of their arguments */
   ECCX_PREP_ECDSA = 1u << 7,    /* eccx_reserve: the working slabs of eccx_ecdsa_verify (u1, u2, x, flags, decoded keys) and
                                    the slabs of the verify-shape ladder it runs (as ECCX_PREP_VAR) */
+  ECCX_PREP_ED25519 = 1u << 8,  /* eccx_reserve (edwards25519): the working slab of eccx_ed25519_verify (u1, u2, decoded keys,
+                                   the ladder's output and flags) and the slabs of the verify-shape ladder it runs */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -201,12 +204,16 @@ enum {
 /* flag values written per unit */
 enum { ECCX_FLAG_FINITE = 0, ECCX_FLAG_INFINITY = 1, ECCX_FLAG_REJECTED = 2 };
 
-/* ECDSA verdicts (eccx_ecdsa_verify), one byte per signature */
+/* signature verdicts (eccx_ecdsa_verify, eccx_ed25519_verify), one byte per signature */
 enum {
-  ECCX_SIG_INVALID = 0,   /* the equation fails: x(R) mod n != r, or R = u1*G + u2*Q is the identity */
+  ECCX_SIG_INVALID = 0,   /* the equation fails.  ECDSA: x(R) mod n != r, or R = u1*G + u2*Q is the identity.
+                             Ed25519: [S]B - [k]A != R */
   ECCX_SIG_VALID = 1,
-  ECCX_SIG_MALFORMED = 2, /* r or s is 0 or >= n (Signature::from_bytes), or a digest_bytes == 0 scalar is >= n */
-  ECCX_SIG_BAD_KEY = 3    /* the public key is non-canonical, off the curve or the identity, or its SEC1 bytes do not decode */
+  ECCX_SIG_MALFORMED = 2, /* ECDSA: r or s is 0 or >= n (Signature::from_bytes), or a digest_bytes == 0 scalar is >= n.
+                             Ed25519: S >= l (Scalar::from_bytes_le), R fails decode_point, or the message's offsets
+                             decrease */
+  ECCX_SIG_BAD_KEY = 3    /* ECDSA: the public key is non-canonical, off the curve or the identity, or its SEC1 bytes do
+                             not decode.  Ed25519: A fails decode_point (small and mixed order keys are legal) */
 };
 
 typedef struct eccx_ctx eccx_ctx;
@@ -311,6 +318,27 @@ int eccx_ecdsa_verify(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests
                       const uint8_t* sigs, const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts);
 int eccx_ecdsa_verify_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_digests, size_t digest_bytes,
                           const void* d_sigs, const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream);
+
+/* Ed25519 verification, batched (src/protocol/ed25519.rs verify, :119-146; PureEdDSA, RFC 8032 §5.1.7 as the
+ * reference implements it: cofactorless, [S]B == R + [k]A).
+ *   msgs    : the messages, concatenated
+ *   offsets : n + 1 uint64; message i is msgs[offsets[i] - offsets[0] .. offsets[i+1] - offsets[0])
+ *             (relative to offsets[0], so any sub-range of a batch is itself a batch)
+ *   sigs    : n x 64, R || S as on the wire (S little-endian)
+ *   pubkeys : n x 32 RFC 8032 encodings
+ *   verdicts: n bytes, ECCX_SIG_*.  MALFORMED before BAD_KEY before the equation.
+ * k = SHA-512(R || A || M) of the bytes as given, read little-endian and reduced mod l.  A of small or mixed order is a
+ * legal key, as in the reference.  On the GPU: A is decoded; one pass checks S < l and R's bytes, hashes R || A || M
+ * and reduces k; the verify shape of eccx_double_scalarmul runs with ECCX_SUBTRACT; a last pass compares the encoding
+ * of [S]B - [k]A with R's bytes and decodes R only where they differ.  opts must be 0 (ECCX_ERR_ARG otherwise).
+ * The host form checks that the offsets never decrease before it touches the device (ECCX_ERR_ARG); msgs may be NULL
+ * when every message is empty.  The _dev form cannot check buffer bounds: a lane whose offsets decrease (against the
+ * next one or against offsets[0]) reads nothing and is MALFORMED.  It enqueues on `stream` without synchronising and
+ * uses the context's Ed25519 slab (grow-only; eccx_reserve with ECCX_PREP_ED25519 sizes it). */
+int eccx_ed25519_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* sigs,
+                        const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts);
+int eccx_ed25519_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_sigs,
+                            const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

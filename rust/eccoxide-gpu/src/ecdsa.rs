@@ -29,7 +29,7 @@ impl Verdict {
     }
 }
 
-fn verdict_of(b: u8) -> Verdict {
+pub(crate) fn verdict_of(b: u8) -> Verdict {
     match b {
         ffi::ECCX_SIG_VALID => Verdict::Valid,
         ffi::ECCX_SIG_MALFORMED => Verdict::Malformed,

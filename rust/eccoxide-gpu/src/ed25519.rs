@@ -1,5 +1,5 @@
 //! edwards25519 (`src/curve/curve25519.rs`): `Point::scale`, `Point::mul_base`, the Ed25519 verification
-//! shape and the RFC 8032 point encoding over batches.
+//! shape, Ed25519 verification itself and the RFC 8032 point encoding over batches.
 use eccoxide::curve::curve25519::{FieldElement, Point, Scalar};
 
 use crate::{ffi, GpuContext, GpuError, Secrecy, Unit};
@@ -102,4 +102,32 @@ pub fn encode_points(ctx: &GpuContext, points: &[Point]) -> Result<Vec<[u8; 32]>
     let mut out = vec![0u8; n * 32];
     ctx.check(unsafe { ffi::eccx_point_compress(ctx.raw(), ID, n, xy.as_ptr(), core::ptr::null(), out.as_mut_ptr(), 0) })?;
     Ok(out.chunks_exact(32).map(|c| c.try_into().unwrap()).collect())
+}
+
+/// `public[i].verify(messages[i], &sigs[i])` (`src/protocol/ed25519.rs` verify, `:119-146`) over a batch, in one call
+/// into the library (`eccx_ed25519_verify`): decoding A and R, the range check of S, k = SHA-512(R || A || M) mod l,
+/// `[S]B - [k]A` and the comparison with R all run on the GPU.  The verdict is `Valid` exactly where the reference's
+/// `verify` returns true; the others say why it does not (`ecdsa::Verdict`: `Malformed` for S >= l or an R that does
+/// not decode, `BadKey` for an A that does not decode, `Invalid` for a failed equation).
+pub fn verify_batch(ctx: &GpuContext, public: &[eccoxide::protocol::ed25519::PublicKey], messages: &[&[u8]],
+                    sigs: &[eccoxide::protocol::ed25519::Signature]) -> Result<Vec<crate::ecdsa::Verdict>, GpuError> {
+    assert_eq!(public.len(), sigs.len());
+    assert_eq!(messages.len(), sigs.len());
+    let n = sigs.len();
+    let (mut k, mut s) = (Vec::with_capacity(n * 32), Vec::with_capacity(n * 64));
+    let mut offsets = Vec::with_capacity(n + 1);
+    let mut msgs = Vec::new();
+    offsets.push(0u64);
+    for i in 0..n {
+        k.extend_from_slice(&public[i].to_bytes());
+        s.extend_from_slice(&sigs[i].to_bytes()); // R || S as on the wire
+        msgs.extend_from_slice(messages[i]);
+        offsets.push(msgs.len() as u64);
+    }
+    let mut verdicts = vec![0u8; n];
+    ctx.check(unsafe {
+        ffi::eccx_ed25519_verify(ctx.raw(), n, if msgs.is_empty() { core::ptr::null() } else { msgs.as_ptr() },
+                                 offsets.as_ptr(), s.as_ptr(), k.as_ptr(), verdicts.as_mut_ptr(), 0)
+    })?;
+    Ok(verdicts.iter().map(|&v| crate::ecdsa::verdict_of(v)).collect())
 }

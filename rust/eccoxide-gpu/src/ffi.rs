@@ -54,13 +54,14 @@ pub const ECCX_PREP_HOST: u32 = 1 << 6;
 pub const ECCX_PREP_CT_GATHER: u32 = 1 << 5;
 pub const ECCX_PREP_CT: u32 = 1 << 4; // ECCX_CT_SCAN: the secret-scalar fixed-base table / variable-base slabs
 pub const ECCX_PREP_ECDSA: u32 = 1 << 7; // eccx_ecdsa_verify's working slabs
+pub const ECCX_PREP_ED25519: u32 = 1 << 8; // eccx_ed25519_verify's working slab
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
 pub const ECCX_FLAG_INFINITY: u8 = 1;
 pub const ECCX_FLAG_REJECTED: u8 = 2;
 
-// ECDSA verdicts, one byte per signature (eccx_ecdsa_verify)
+// signature verdicts, one byte per signature (eccx_ecdsa_verify, eccx_ed25519_verify)
 pub const ECCX_SIG_INVALID: u8 = 0;
 pub const ECCX_SIG_VALID: u8 = 1;
 pub const ECCX_SIG_MALFORMED: u8 = 2;
@@ -111,6 +112,13 @@ extern "C" {
     pub fn eccx_ecdsa_verify_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_digests: *const c_void, digest_bytes: usize,
                                  d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
                                  stream: *mut c_void) -> c_int;
+
+    // Ed25519 verification, batched                         protocol::ed25519 verify (PublicKey::verify)
+    pub fn eccx_ed25519_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, sigs: *const u8,
+                               pubkeys: *const u8, verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_ed25519_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void,
+                                   d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
+                                   stream: *mut c_void) -> c_int;
 
     // X25519 over a batch                                    protocol::x25519::x25519
     pub fn eccx_x25519(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,

@@ -33,6 +33,7 @@ C_TO_RUST = {
     "uint32_t": "u32",
     "const uint8_t*": "*const u8",
     "uint8_t*": "*mut u8",
+    "const uint64_t*": "*const u64",
     "const void*": "*const c_void",
     "void*": "*mut c_void",
     "eccx_ctx*": "*mut eccx_ctx",

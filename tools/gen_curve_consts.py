@@ -58,6 +58,7 @@ P25519 = 2**255 - 19
 ED_D = (-121665 * pow(121666, -1, P25519)) % P25519
 ED_GX = 0x216936D3CD6E53FEC0A4E231FDD6DC5C692CC7609525A7B2C9562D608F25D51A
 ED_GY = 0x6666666666666666666666666666666666666666666666666666666666666658
+ED25519_L = 2**252 + 27742317777372353535851937790883648493  # order of the base point (cofactor 8)
 
 
 def limbs(x, n):
@@ -389,6 +390,17 @@ def main():
         out.append("  static constexpr int NBITS = %d;  // qlen: bits2int keeps this many leading bits of a digest" % n.bit_length())
         emit_field(out, n, L)
         out.append("};")
+    # the order l of edwards25519's base point (kernels_ed25519_verify.hpp): S < l, SHA-512(R || A || M) mod l.  General
+    # Montgomery as above; NBITS is l's bit length (no bits2int here: the wide hash is reduced exactly)
+    ell = ED25519_L
+    out.append("")
+    out.append("struct ED25519_ORD {  // l, the order of the base point of edwards25519")
+    out.append("  static constexpr int L = 8;   // 32-bit limbs")
+    out.append("  static constexpr int FB = 32;  // bytes of an element (= SB)")
+    out.append("  static constexpr int SB = 32;  // scalar bytes")
+    out.append("  static constexpr int NBITS = %d;  // bit length of l" % ell.bit_length())
+    emit_field(out, ell, 8)
+    out.append("};")
     sys.stdout.write("\n".join(out) + "\n")
 
 
