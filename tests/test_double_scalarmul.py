@@ -118,6 +118,9 @@ def test_fused_accumulation_special_cases(engine, oracle, curve):
         want = oracle.base(curve, b"".join(t.to_bytes(c.sb, "big") for t in tot))
         assert out == want[0] and flags == want[1], (curve, subtract)
         assert any(f == 1 for f in flags)   # some of them are the point at infinity
+        # the options ECDSA verification passes: the same x and flags
+        xs, flx = engine.double_scalarmul(curve, u1, u2, g * n, subtract=subtract, x_only=True, validate=True)
+        assert flx == flags and xs == b"".join(out[i * pb: i * pb + c.fb] for i in range(n)), (curve, subtract, "x_only")
 
 
 def test_ed25519_double_scalarmul_matches_oracle(engine, oracle):

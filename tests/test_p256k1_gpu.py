@@ -191,6 +191,48 @@ def test_ecdsa_verify_shape(engine):
         assert full[64 * i: 64 * i + 64] == K.affine_bytes(want)[0]
 
 
+def test_fused_accumulation_special_cases(engine):
+    """tests/test_double_scalarmul.py's test of the same name, for the curve the C oracle does not have: (u1, u2) that make
+    the comb of u1 G and the ladder's u2 Q collide (accumulator == table entry: the doubling branch; == its negative:
+    infinity) or leave a half at infinity, with Q = G, -G, sigma(G), sigma^2(G) (Q = q G for q = 1, n - 1, lambda,
+    lambda^2), both signs, plain and with the options ECDSA verification passes (x only, keys validated)."""
+    from tests import ecdsa_ref as E
+
+    rng = random.Random(99)
+    pairs = []
+    for w, d in ((0, 1), (0, 200), (1, 7), (5, 255), (30, 3)):
+        k = d << (8 * w)
+        pairs += [(k, k), (N - k, k), (k, N - k)]
+    pairs += [(0, 0), (0, N), (N, 0), (5, 0), (0, 5), (N - 1, 1), (1, N - 1)]
+    for _ in range(8):
+        k = rng.randrange(1, N)
+        pairs += [(N - k, k), (k, k)]
+    lam = K.LAMBDA
+    bases = [(1, K.G), (N - 1, K.neg(K.G)), (lam, K.sigma(K.G)), (lam * lam % N, K.sigma(K.sigma(K.G)))]
+    for q, Q in bases:
+        assert E.mul(K.K1, q) == Q
+        # the same collisions where Q is not G: u2 Q = +-k G
+        qi = pow(q, -1, N)
+        extra = []
+        for w, d in ((0, 1), (0, 200), (1, 7), (2, 65535), (5, 255), (30, 3)):
+            k = d << (8 * w)
+            extra += [(k, k * qi % N), (N - k, k * qi % N), (k, (N - k) * qi % N), (0, k * qi % N)]
+        these = pairs + extra
+        n = len(these)
+        u1 = b"".join(kb(a) for a, _ in these)
+        u2 = b"".join(kb(b) for _, b in these)
+        qs = K.point_bytes(Q) * n
+        for subtract in (False, True):
+            out, flags = engine.double_scalarmul(C, u1, u2, qs, subtract=subtract)
+            for i, (a, b) in enumerate(these):
+                B = E.mul(K.K1, b, Q)
+                want, wf = K.affine_bytes(R_add(E.mul(K.K1, a), K.neg(B) if subtract else B))
+                assert flags[i] == wf and out[64 * i: 64 * i + 64] == want, (hex(q), subtract, i, hex(a), hex(b))
+            assert any(f == 1 for f in flags) and any(f == 0 for f in flags)
+            xs, flx = engine.double_scalarmul(C, u1, u2, qs, subtract=subtract, x_only=True, validate=True)
+            assert flx == flags and xs == b"".join(out[64 * i: 64 * i + 32] for i in range(n)), (hex(q), subtract, "x_only")
+
+
 def test_sec1_codec(engine):
     rng = random.Random(61)
     pts = rand_points(rng, 200) + [K.G, K.neg(K.G)]
