@@ -75,6 +75,9 @@ struct eccx_ctx {
   // the same for eccx_ed25519_verify_dev (u1, u2, decoded keys, the ladder's x || y and flags)
   uint8_t* ed = nullptr;
   size_t ed_cap = 0;
+  // the same for eccx_ed25519_sign_dev / eccx_ed25519_public_key_dev (the comb's scalars r and a, its x || y and flags)
+  uint8_t* edsign = nullptr;
+  size_t edsign_cap = 0;
   static constexpr int NEV = 10;
   hipEvent_t evs[NEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::mutex err_mu;       // err is written by whichever host thread's call failed last
@@ -209,6 +212,21 @@ int ensure_ed(eccx_ctx* ctx, size_t n, EdSlab* out) {
   out->lflags = out->u2 + align16(n * 32);
   out->keys = out->lflags + align16(n);
   out->pts = out->keys + align16(n * 64);
+  return ECCX_OK;
+}
+
+// the Ed25519 signing slab for n signatures, 2n lanes of the comb: scalars (r in rows 0 .. n, a in rows n .. 2n), the
+// comb's x || y (2n x 64) and flags (2n)
+struct EdSignSlab {
+  uint8_t *scal, *pts, *lflags;
+};
+size_t ed_sign_slab_bytes(size_t n) { return align16(2 * n * 32) + align16(2 * n * 64) + 2 * n; }
+int ensure_ed_sign(eccx_ctx* ctx, size_t n, EdSignSlab* out) {
+  const int rc = grow_slab(ctx, &ctx->edsign, &ctx->edsign_cap, ed_sign_slab_bytes(n));
+  if (rc || !out) return rc;
+  out->scal = ctx->edsign;
+  out->pts = out->scal + align16(2 * n * 32);
+  out->lflags = out->pts + align16(2 * n * 64);
   return ECCX_OK;
 }
 
@@ -746,6 +764,7 @@ void eccx_shutdown(eccx_ctx* ctx) {
     if (b) (void)hipFree(b);
   if (ctx->ecdsa) (void)hipFree(ctx->ecdsa);
   if (ctx->ed) (void)hipFree(ctx->ed);
+  if (ctx->edsign) (void)hipFree(ctx->edsign);
   for (auto& e : ctx->evs)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -847,6 +866,11 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     rc = ensure_ed(ctx, max_n, nullptr);
     if (rc) return rc;
   }
+  if ((what & ECCX_PREP_ED25519_SIGN) && ops->ed_sign_expand) {  // eccx_ed25519_sign's, and the comb's rows for 2 max_n lanes
+    rc = ensure_rows(ctx, ops, 2 * max_n);
+    if (!rc) rc = ensure_ed_sign(ctx, max_n, nullptr);
+    if (rc) return rc;
+  }
   // slab of the reference-mirroring ladder (also what ECCX_CT_SCAN runs on a curve without a scanning fast ladder)
   const bool mirror_slab = (what & ECCX_PREP_MIRROR) || ((what & ECCX_PREP_CT) && !ops->var_ct);
   if (mirror_slab && ops->info.row_words) {
@@ -864,7 +888,7 @@ size_t eccx_device_bytes(const eccx_ctx* ctx) {
   std::lock_guard<std::mutex> g2(c->scratch_mu);
   size_t io = 0;
   for (size_t b : c->io_cap) io += b;
-  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap + c->ed_cap;
+  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap + c->ed_cap + c->edsign_cap;
 }
 
 int eccx_scalarmul_var_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points,
@@ -1293,6 +1317,123 @@ int eccx_ed25519_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint
         if (e == hipSuccess && b > a) e = hipMemcpyAsync(d_m + a, msgs + a, b - a, hipMemcpyHostToDevice, st);
         return e;
       });
+}
+
+// eccx_ed25519_sign / _public_key: opts is 0 or ECCX_CT_GATHER (ECCX_CT_SCAN is implied, not named)
+static int ed_sign_opts(eccx_ctx* ctx, uint32_t opts) {
+  if (opts & ~(uint32_t)ECCX_CT_GATHER) return arg_err(ctx, "eccx_ed25519_sign: opts must be 0 or ECCX_CT_GATHER");
+  return ECCX_OK;
+}
+
+int eccx_ed25519_public_key_dev(eccx_ctx* ctx, size_t n, const void* d_seeds, void* d_pubkeys, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = ed_sign_opts(ctx, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!d_seeds || !d_pubkeys) return arg_err(ctx, "null buffer");
+  const CurveOps* ops = ops_of(ECCX_ED25519);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EdSignSlab w;
+  int rc = ensure_ed_sign(ctx, n, &w);
+  if (rc) return rc;
+  // a = clamp(SHA-512(seed)[0..32]) mod l; A = [a]B on the secret-scalar comb; encode, and wipe a
+  HIP_TRY(ctx, ops->ed_sign_expand(flat_grid(ctx, n), s, n, nullptr, nullptr, static_cast<const uint8_t*>(d_seeds), w.scal));
+  rc = eccx_scalarmul_base_dev(ctx, ECCX_ED25519, n, w.scal, w.pts, w.lflags, nullptr, ECCX_CT_SCAN | (opts & ECCX_CT_GATHER), stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, ops->ed_pubkey_finish(flat_grid(ctx, n), s, n, w.pts, w.scal, static_cast<uint8_t*>(d_pubkeys)));
+  return ECCX_OK;
+}
+
+int eccx_ed25519_public_key(eccx_ctx* ctx, size_t n, const uint8_t* seeds, uint8_t* pubkeys, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = ed_sign_opts(ctx, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!seeds || !pubkeys) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t *d_s = nullptr, *d_k = nullptr;
+  int rc = ensure_io(ctx, IO_P, n * 32, &d_s);
+  if (!rc) rc = ensure_io(ctx, IO_A, n * 32, &d_k);
+  if (rc) return rc;
+  const HostIn ins[1] = {{d_s, seeds, 32}};
+  const HostOut outs[1] = {{pubkeys, d_k, 32}};
+  rc = host_pipeline(ctx, n, ins, 1, outs, 1, /*chunked=*/true, [&](size_t lo, size_t cnt) {
+    return eccx_ed25519_public_key_dev(ctx, cnt, d_s + lo * 32, d_k + lo * 32, opts, ctx->stream);
+  });
+  // the device-side copy of the seeds does not outlive the call
+  const hipError_t e1 = hipMemsetAsync(d_s, 0, n * 32, ctx->stream), e2 = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e1);
+  HIP_TRY(ctx, e2);
+  return ECCX_OK;
+}
+
+int eccx_ed25519_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_seeds,
+                          const void* d_pubkeys, void* d_sigs, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = ed_sign_opts(ctx, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!d_msgs || !d_offsets || !d_seeds || !d_sigs) return arg_err(ctx, "null buffer");
+  const CurveOps* ops = ops_of(ECCX_ED25519);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EdSignSlab w;
+  int rc = ensure_ed_sign(ctx, n, &w);
+  if (rc) return rc;
+  const uint8_t* msgs = static_cast<const uint8_t*>(d_msgs);
+  const uint64_t* offsets = static_cast<const uint64_t*>(d_offsets);
+  HIP_TRY(ctx, ops->ed_sign_expand(flat_grid(ctx, n), s, n, msgs, offsets, static_cast<const uint8_t*>(d_seeds), w.scal));
+  // one launch of the secret-scalar comb: R = [r]B in rows 0 .. n and, where the keys are derived, A = [a]B in rows n .. 2n
+  const size_t lanes = d_pubkeys ? n : 2 * n;
+  rc = eccx_scalarmul_base_dev(ctx, ECCX_ED25519, lanes, w.scal, w.pts, w.lflags, nullptr, ECCX_CT_SCAN | (opts & ECCX_CT_GATHER),
+                               stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, ops->ed_sign_finish(flat_grid(ctx, n), s, n, msgs, offsets, static_cast<const uint8_t*>(d_pubkeys), w.pts, w.scal,
+                                   static_cast<uint8_t*>(d_sigs)));
+  return ECCX_OK;
+}
+
+int eccx_ed25519_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* seeds,
+                      const uint8_t* pubkeys, uint8_t* sigs, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = ed_sign_opts(ctx, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!offsets || !seeds || !sigs) return arg_err(ctx, "null buffer");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return arg_err(ctx, "eccx_ed25519_sign: the offsets decrease");
+  const size_t total = (size_t)(offsets[n] - offsets[0]);
+  if (total && !msgs) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t *d_m = nullptr, *d_o = nullptr, *d_s = nullptr, *d_k = nullptr, *d_g = nullptr;
+  int rc = ensure_io(ctx, IO_J, total ? total : 1, &d_m);
+  if (!rc) rc = ensure_io(ctx, IO_K, (n + 1) * sizeof(uint64_t), &d_o);
+  if (!rc) rc = ensure_io(ctx, IO_P, n * 32, &d_s);
+  if (!rc && pubkeys) rc = ensure_io(ctx, IO_A, n * 32, &d_k);
+  if (!rc) rc = ensure_io(ctx, IO_O, n * 64, &d_g);
+  if (rc) return rc;
+  const HostIn ins[2] = {{d_s, seeds, 32}, {d_k, pubkeys, 32}};
+  const HostOut outs[1] = {{sigs, d_g, 64}};
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_o);
+  // chunks as in eccx_ed25519_verify: each a batch of its own, messages at the same places on the device as on the host
+  rc = host_pipeline_x(
+      ctx, n, ins, 2, outs, 1, /*chunked=*/true,
+      [&](size_t lo, size_t cnt) {
+        return eccx_ed25519_sign_dev(ctx, cnt, d_m + (offsets[lo] - offsets[0]), d_off + lo, d_s + lo * 32,
+                                     pubkeys ? d_k + lo * 32 : nullptr, d_g + lo * 64, opts, ctx->stream);
+      },
+      [&](size_t lo, size_t cnt, hipStream_t st) {
+        const size_t first = lo == 0 ? 0 : lo + 1;  // offsets[lo] came with the chunk before
+        hipError_t e = hipMemcpyAsync(d_o + first * sizeof(uint64_t), offsets + first, (lo + cnt + 1 - first) * sizeof(uint64_t),
+                                      hipMemcpyHostToDevice, st);
+        const size_t a = (size_t)(offsets[lo] - offsets[0]), b = (size_t)(offsets[lo + cnt] - offsets[0]);
+        if (e == hipSuccess && b > a) e = hipMemcpyAsync(d_m + a, msgs + a, b - a, hipMemcpyHostToDevice, st);
+        return e;
+      });
+  // the device-side copy of the seeds does not outlive the call
+  const hipError_t e1 = hipMemsetAsync(d_s, 0, n * 32, ctx->stream), e2 = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e1);
+  HIP_TRY(ctx, e2);
+  return ECCX_OK;
 }
 
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,

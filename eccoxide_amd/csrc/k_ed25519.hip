@@ -1,6 +1,7 @@
 // Kernel instantiations for edwards25519 (see kernels.hpp).
 #include "kernels_codec.hpp"
 #include "kernels_ct.hpp"
+#include "kernels_ed25519_sign.hpp"
 #include "kernels_ed25519_verify.hpp"
 #include "launch.hpp"
 
@@ -131,6 +132,22 @@ hipError_t ed_verify_finish_(int grid, hipStream_t s, size_t n, const uint8_t* s
   hipLaunchKernelGGL(k_ed_verify_finish<ED25519U>, dim3(grid), dim3(WG), 0, s, n, sigs, pts, verdicts);
   return hipGetLastError();
 }
+// Ed25519 signing and key derivation (kernels_ed25519_sign.hpp): the passes before and after the secret-scalar comb
+hipError_t ed_sign_expand_(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* seeds,
+                           uint8_t* scal) {
+  if (offsets) hipLaunchKernelGGL((k_ed_sign_expand<ED25519_ORD, true>), dim3(grid), dim3(WG), 0, s, n, msgs, offsets, seeds, scal);
+  else hipLaunchKernelGGL((k_ed_sign_expand<ED25519_ORD, false>), dim3(grid), dim3(WG), 0, s, n, nullptr, nullptr, seeds, scal);
+  return hipGetLastError();
+}
+hipError_t ed_sign_finish_(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* pubkeys,
+                           const uint8_t* pts, uint8_t* scal, uint8_t* sigs) {
+  hipLaunchKernelGGL((k_ed_sign_finish<ED25519, ED25519_ORD>), dim3(grid), dim3(WG), 0, s, n, msgs, offsets, pubkeys, pts, scal, sigs);
+  return hipGetLastError();
+}
+hipError_t ed_pubkey_finish_(int grid, hipStream_t s, size_t n, const uint8_t* pts, uint8_t* scal, uint8_t* out) {
+  hipLaunchKernelGGL((k_ed_pubkey_finish<ED25519, ED25519_ORD>), dim3(grid), dim3(WG), 0, s, n, pts, scal, out);
+  return hipGetLastError();
+}
 }  // namespace
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u, uint32_t* rows,
                                 uint8_t* flags, uint32_t opts) {
@@ -161,6 +178,9 @@ const CurveOps& ops_ED25519() {
     t.var_ct_grid = var_ct_grid_;
     t.ed_verify_prepare = ed_verify_prepare_;
     t.ed_verify_finish = ed_verify_finish_;
+    t.ed_sign_expand = ed_sign_expand_;
+    t.ed_sign_finish = ed_sign_finish_;
+    t.ed_pubkey_finish = ed_pubkey_finish_;
     return t;
   }();
   return o;

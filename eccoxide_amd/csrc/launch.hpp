@@ -139,6 +139,16 @@ struct CurveOps {
                                   const uint8_t* sigs, const uint8_t* pubkeys, const uint8_t* key_flags, uint8_t* u1, uint8_t* u2,
                                   uint8_t* verdicts);
   hipError_t (*ed_verify_finish)(int grid, hipStream_t s, size_t n, const uint8_t* sigs, const uint8_t* pts, uint8_t* verdicts);
+  // Ed25519 signing and key derivation (kernels_ed25519_sign.hpp; edwards25519 only).  ed_sign_expand hashes the seeds and
+  // writes the big-endian scalars of the secret-scalar comb into scal: with offsets, r = SHA-512(prefix || M) mod l in rows
+  // 0 .. n and the clamped a mod l in rows n .. 2n; with offsets == null (key derivation) a alone in rows 0 .. n.
+  // ed_sign_finish reads the comb's affine rows pts (R in rows 0 .. n; A in rows n .. 2n where pubkeys == null), hashes
+  // R || A || M, writes R || S = r + k a mod l and zeroes both scalar rows.  ed_pubkey_finish encodes n rows and zeroes a.
+  hipError_t (*ed_sign_expand)(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* seeds,
+                               uint8_t* scal);
+  hipError_t (*ed_sign_finish)(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* pubkeys,
+                               const uint8_t* pts, uint8_t* scal, uint8_t* sigs);
+  hipError_t (*ed_pubkey_finish)(int grid, hipStream_t s, size_t n, const uint8_t* pts, uint8_t* scal, uint8_t* out);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above

@@ -30,6 +30,7 @@ PUBKEY_SEC1 = 1 << 12
 PREP_VAR, PREP_BASE, PREP_BASE_LDS, PREP_MIRROR, PREP_CT, PREP_CT_GATHER, PREP_HOST = 1, 2, 4, 8, 16, 32, 64
 PREP_ECDSA = 128
 PREP_ED25519 = 256
+PREP_ED25519_SIGN = 512
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
 SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
@@ -141,14 +142,16 @@ class Engine:
                                            | (PREP_CT if ct else 0) | (PREP_CT_GATHER if ct_gather else 0)))
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
-                ecdsa: bool = False, ed25519: bool = False):
+                ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
-        ed25519_verify (curve "ed25519")."""
+        ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
+        row buffer for 2 * max_n lanes."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
-                                           | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)))
+                                           | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)
+                                           | (PREP_ED25519_SIGN if ed25519_sign else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -338,6 +341,82 @@ class Engine:
         self._check(self._lib.eccx_ed25519_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), sigs.data_ptr(),
                                                       pubkeys.data_ptr(), verdicts.data_ptr(), 0, stream))
         return verdicts
+
+    def ed25519_public_key(self, seeds: bytes, *, ct_gather: bool = False) -> bytes:
+        """Ed25519 public keys of a batch of seeds (eccx_ed25519_public_key; SecretKey::public_key): seeds n x 32, the
+        RFC 8032 secret keys.  Returns n x 32 encodings.  The secret-scalar comb always runs; ct_gather selects its
+        cross-lane lookup (ECCX_CT_GATHER)."""
+        if len(seeds) % 32:
+            raise ValueError("seeds must be n x 32 bytes")
+        n = len(seeds) // 32
+        out = ctypes.create_string_buffer(max(1, 32 * n))
+        self._check(self._lib.eccx_ed25519_public_key(self._ctx, n, seeds, out, CT_GATHER if ct_gather else 0))
+        return out.raw[:32 * n]
+
+    def ed25519_public_key_t(self, seeds, pubkeys=None, *, ct_gather: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of ed25519_public_key (eccx_ed25519_public_key_dev): seeds n x 32 (torch.uint8, CUDA);
+        enqueued on `stream` (default: torch's current stream); returns the n x 32 tensor of encodings."""
+        import torch
+
+        n = self._units(seeds, 32, "seeds")
+        if pubkeys is None:
+            pubkeys = torch.empty((n * 32,), dtype=torch.uint8, device=seeds.device)
+        self._tensors(n, ("seeds", seeds, 32), ("pubkeys", pubkeys, 32))
+        if stream is None:
+            stream = torch.cuda.current_stream(seeds.device).cuda_stream
+        self._check(self._lib.eccx_ed25519_public_key_dev(self._ctx, n, seeds.data_ptr(), pubkeys.data_ptr(),
+                                                          CT_GATHER if ct_gather else 0, stream))
+        return pubkeys
+
+    def ed25519_sign(self, messages, seeds: bytes, pubkeys: Optional[bytes] = None, *, ct_gather: bool = False) -> bytes:
+        """Ed25519 signatures of a batch (eccx_ed25519_sign): messages is a list of n byte strings, seeds n x 32.
+        pubkeys None is SecretKey::sign (A derived on the GPU, two fixed-base multiplications per signature); n x 32
+        encodings are Keypair::sign (one) -- each MUST be ed25519_public_key's output for its seed: any other key gives a
+        signature that does not verify and gives away the secret scalar.  Returns n x 64 bytes, R || S."""
+        import numpy as np
+
+        n = len(messages)
+        if len(seeds) != 32 * n or (pubkeys is not None and len(pubkeys) != 32 * n):
+            raise ValueError("seeds (and pubkeys) must be n x 32 bytes for n messages")
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(m) for m in messages], out=offsets[1:])
+        msgs = b"".join(bytes(m) for m in messages)
+        sigs = ctypes.create_string_buffer(max(1, 64 * n))
+        self._check(self._lib.eccx_ed25519_sign(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, seeds, pubkeys, sigs,
+                                                CT_GATHER if ct_gather else 0))
+        return sigs.raw[:64 * n]
+
+    def ed25519_sign_t(self, msgs, offsets, seeds, pubkeys=None, sigs=None, *, ct_gather: bool = False,
+                       stream: Optional[int] = None, check_bounds: bool = True):
+        """Device-tensor form of ed25519_sign (eccx_ed25519_sign_dev): msgs, offsets as in ed25519_verify_t, seeds n x 32,
+        pubkeys None or n x 32 (see ed25519_sign).  Enqueued on `stream` (default: torch's current stream); returns the
+        n x 64 signature tensor.  A lane whose offsets decrease gets 64 zero bytes.  check_bounds as in ed25519_verify_t."""
+        import torch
+
+        n = self._units(seeds, 32, "seeds")
+        if offsets.dtype not in (torch.int64, torch.uint64) or offsets.numel() != n + 1 or not offsets.is_contiguous():
+            raise ValueError(f"offsets must be a contiguous int64 tensor of n + 1 = {n + 1} entries")
+        if not offsets.is_cuda or not msgs.is_cuda or msgs.dtype != torch.uint8 or not msgs.is_contiguous():
+            raise ValueError("msgs (contiguous uint8) and offsets must be CUDA tensors")
+        if sigs is None:
+            sigs = torch.empty((n * 64,), dtype=torch.uint8, device=seeds.device)
+        self._tensors(n, ("seeds", seeds, 32), ("pubkeys", pubkeys, 32), ("sigs", sigs, 64))
+        for name, t in (("msgs", msgs), ("offsets", offsets)):
+            if t.device.index != self.device:
+                raise ValueError(f"{name}: tensor lives on cuda:{t.device.index}, this engine is bound to cuda:{self.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(seeds.device).cuda_stream
+        if check_bounds and n:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=seeds.device)):
+                lo, hi, first = (int(v) for v in torch.stack([offsets.min(), offsets.max(), offsets[0]]).cpu())
+            if lo < 0 or hi - first > msgs.numel():
+                raise ValueError(f"offsets span {hi - first} bytes from offsets[0] (min {lo}); msgs holds {msgs.numel()}")
+        if msgs.numel() == 0:  # every message empty: any valid address
+            msgs = torch.zeros((1,), dtype=torch.uint8, device=seeds.device)
+        self._check(self._lib.eccx_ed25519_sign_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), seeds.data_ptr(),
+                                                    pubkeys.data_ptr() if pubkeys is not None else None, sigs.data_ptr(),
+                                                    CT_GATHER if ct_gather else 0, stream))
+        return sigs
 
     def compressed_bytes(self, curve) -> int:
         """Bytes per compressed point: FB + 1 (SEC1), 48 (zcash G1), 32 (RFC 8032)."""

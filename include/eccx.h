@@ -21,6 +21,8 @@
  *   eccx_double_scalarmul[_dev]  u1*G + u2*Q                     src/protocol/ecdsa.rs:215, ed25519.rs:145
  *   eccx_ecdsa_verify[_dev]      ECDSA verification              src/protocol/ecdsa.rs:200-222
  *   eccx_ed25519_verify[_dev]    Ed25519 verification            src/protocol/ed25519.rs:119-146
+ *   eccx_ed25519_public_key[_dev]  SecretKey::public_key        src/protocol/ed25519.rs:62-80, 175-190
+ *   eccx_ed25519_sign[_dev]      SecretKey::sign / Keypair::sign   src/protocol/ed25519.rs:91-117, 192-247
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
@@ -195,6 +197,8 @@ enum {
                                    the slabs of the verify-shape ladder it runs (as ECCX_PREP_VAR) */
   ECCX_PREP_ED25519 = 1u << 8,  /* eccx_reserve (edwards25519): the working slab of eccx_ed25519_verify (u1, u2, decoded keys,
                                    the ladder's output and flags) and the slabs of the verify-shape ladder it runs */
+  ECCX_PREP_ED25519_SIGN = 1u << 9, /* eccx_reserve (edwards25519): the working slab of eccx_ed25519_sign / _public_key (the
+                                   comb's scalars, its output and flags) and the fixed-base row buffer, for 2 * max_n lanes */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -339,6 +343,36 @@ int eccx_ed25519_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint
                         const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts);
 int eccx_ed25519_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_sigs,
                             const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream);
+
+/* Ed25519 key derivation and signing, batched (src/protocol/ed25519.rs SecretKey::public_key, SecretKey::sign,
+ * Keypair::sign; RFC 8032 §5.1.5 and §5.1.6, PureEdDSA).
+ *   seeds   : n x 32, the RFC 8032 secret keys
+ *   pubkeys : n x 32 RFC 8032 encodings (output of eccx_ed25519_public_key; input of eccx_ed25519_sign, or NULL)
+ *   msgs, offsets : as in eccx_ed25519_verify (n + 1 uint64, relative to offsets[0])
+ *   sigs    : n x 64, R || S as on the wire
+ * On the GPU, all of it: h = SHA-512(seed), a = clamp(h[0..32]) mod l, r = SHA-512(h[32..64] || M) mod l; the secret-scalar
+ * fixed-base comb of eccx_scalarmul_base (ECCX_CT_SCAN is implied; the default comb never runs) for R = [r]B; k =
+ * SHA-512(R || A || M) mod l; S = r + k a mod l.  No secret scalar crosses the ABI, and the device-side a and r are
+ * overwritten with zeros by the last pass.
+ *   pubkeys == NULL  SecretKey::sign: A = [a]B is derived beside R in the same launch of the comb (2n lanes).
+ *   pubkeys != NULL  Keypair::sign: one multiplication per signature; A is used only inside the hash.  A supplied key MUST
+ *                    be the one eccx_ed25519_public_key returns for that seed: with any other key the signature does not
+ *                    verify, AND a pair of signatures of one message under two keys gives away the secret scalar a
+ *                    (two equations S = r + k a with the same r and different known k).
+ * opts: 0, or ECCX_CT_GATHER for the cross-lane lookup under that option's caveat; anything else is ECCX_ERR_ARG.
+ * n == 0 returns ECCX_OK whatever the pointers.  The seed, h, a, the prefix and r steer no branch and no memory address
+ * (SIDE CHANNELS above; profiles/ed25519_sign_isa_ct.txt); the message, its length, R, A, k and S are public.
+ * The host forms check that the offsets never decrease before they touch the device (ECCX_ERR_ARG), take msgs == NULL when
+ * every message is empty, and clear their device-side copy of the seeds before returning.  The _dev forms enqueue on `stream`
+ * without synchronising and use the context's signing slab (grow-only; eccx_reserve with ECCX_PREP_ED25519_SIGN sizes it,
+ * eccx_prepare with ECCX_PREP_CT / ECCX_PREP_CT_GATHER builds the table); a lane whose offsets decrease (against the next
+ * one or against offsets[0]) reads nothing and gets 64 zero bytes, the other lanes stand.  Signing has no other failure. */
+int eccx_ed25519_public_key(eccx_ctx* ctx, size_t n, const uint8_t* seeds, uint8_t* pubkeys, uint32_t opts);
+int eccx_ed25519_public_key_dev(eccx_ctx* ctx, size_t n, const void* d_seeds, void* d_pubkeys, uint32_t opts, void* stream);
+int eccx_ed25519_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* seeds,
+                      const uint8_t* pubkeys, uint8_t* sigs, uint32_t opts);
+int eccx_ed25519_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_seeds,
+                          const void* d_pubkeys, void* d_sigs, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

@@ -1,5 +1,5 @@
 //! edwards25519 (`src/curve/curve25519.rs`): `Point::scale`, `Point::mul_base`, the Ed25519 verification
-//! shape, Ed25519 verification itself and the RFC 8032 point encoding over batches.
+//! shape, Ed25519 verification, key derivation and signing themselves and the RFC 8032 point encoding over batches.
 use eccoxide::curve::curve25519::{FieldElement, Point, Scalar};
 
 use crate::{ffi, GpuContext, GpuError, Secrecy, Unit};
@@ -49,7 +49,8 @@ pub fn scale_batch(ctx: &GpuContext, points: &[Point], scalars: &[Scalar], secre
     Ok(parse_points(&out, &flags))
 }
 
-/// `out[i] = Point::mul_base(&scalars[i])` (curve25519.rs:840-851): Ed25519 key generation / signing.
+/// `out[i] = Point::mul_base(&scalars[i])` (curve25519.rs:840-851).  Ed25519 key generation and signing have entry
+/// points of their own (`public_keys_batch`, `sign_batch`) that keep the secret scalars on the GPU.
 pub fn mul_base_batch(ctx: &GpuContext, scalars: &[Scalar], secrecy: Secrecy) -> Result<Vec<Unit<Point>>, GpuError> {
     let n = scalars.len();
     let mut k = Vec::with_capacity(n * 32);
@@ -130,4 +131,65 @@ pub fn verify_batch(ctx: &GpuContext, public: &[eccoxide::protocol::ed25519::Pub
                                  offsets.as_ptr(), s.as_ptr(), k.as_ptr(), verdicts.as_mut_ptr(), 0)
     })?;
     Ok(verdicts.iter().map(|&v| crate::ecdsa::verdict_of(v)).collect())
+}
+
+/// `secret[i].public_key()` (`src/protocol/ed25519.rs:183-185`, `expand_secret` `:62-80`) over a batch, in one call into
+/// the library (`eccx_ed25519_public_key`): SHA-512 of the seed, the clamp, the reduction mod l, `[a]B` on the
+/// secret-scalar fixed-base kernels and the encoding all run on the GPU; no secret scalar crosses the boundary.
+/// `gather` selects the cross-lane lookup (`ECCX_CT_GATHER`, see `eccx.h`).
+pub fn public_keys_batch(ctx: &GpuContext, secret: &[eccoxide::protocol::ed25519::SecretKey], gather: bool)
+                         -> Result<Vec<eccoxide::protocol::ed25519::PublicKey>, GpuError> {
+    let n = secret.len();
+    let mut seeds = Vec::with_capacity(n * 32);
+    for s in secret {
+        seeds.extend_from_slice(&s.to_bytes());
+    }
+    let mut keys = vec![0u8; n * 32];
+    let rc = unsafe {
+        ffi::eccx_ed25519_public_key(ctx.raw(), n, seeds.as_ptr(), keys.as_mut_ptr(), if gather { ffi::ECCX_CT_GATHER } else { 0 })
+    };
+    for b in &mut seeds {
+        *b = 0; // the host-side copy of the seeds does not outlive the call
+    }
+    ctx.check(rc)?;
+    Ok(keys.chunks_exact(32).map(|c| eccoxide::protocol::ed25519::PublicKey::from_bytes(c.try_into().unwrap())).collect())
+}
+
+/// `secret[i].sign(messages[i])` (`SecretKey::sign`, `:187-189`; `public` = `None`) or `Keypair::sign` (`:239-247`;
+/// `public` = the keys) over a batch, in one call into the library (`eccx_ed25519_sign`): both hashes, both reductions,
+/// `[r]B` (and `[a]B` where the keys are derived) on the secret-scalar fixed-base kernels and `S = r + k a mod l` run on
+/// the GPU.  A supplied key MUST be `public_keys_batch`'s output for its seed: with any other key the signature does not
+/// verify and gives away the secret scalar.
+pub fn sign_batch(ctx: &GpuContext, secret: &[eccoxide::protocol::ed25519::SecretKey],
+                  public: Option<&[eccoxide::protocol::ed25519::PublicKey]>, messages: &[&[u8]], gather: bool)
+                  -> Result<Vec<eccoxide::protocol::ed25519::Signature>, GpuError> {
+    assert_eq!(secret.len(), messages.len());
+    let n = secret.len();
+    let mut seeds = Vec::with_capacity(n * 32);
+    let mut offsets = Vec::with_capacity(n + 1);
+    let mut msgs = Vec::new();
+    offsets.push(0u64);
+    for i in 0..n {
+        seeds.extend_from_slice(&secret[i].to_bytes());
+        msgs.extend_from_slice(messages[i]);
+        offsets.push(msgs.len() as u64);
+    }
+    let mut keys = Vec::new();
+    if let Some(p) = public {
+        assert_eq!(p.len(), n);
+        for k in p {
+            keys.extend_from_slice(&k.to_bytes());
+        }
+    }
+    let mut sigs = vec![0u8; n * 64];
+    let rc = unsafe {
+        ffi::eccx_ed25519_sign(ctx.raw(), n, if msgs.is_empty() { core::ptr::null() } else { msgs.as_ptr() }, offsets.as_ptr(),
+                               seeds.as_ptr(), if public.is_some() { keys.as_ptr() } else { core::ptr::null() },
+                               sigs.as_mut_ptr(), if gather { ffi::ECCX_CT_GATHER } else { 0 })
+    };
+    for b in &mut seeds {
+        *b = 0; // the host-side copy of the seeds does not outlive the call
+    }
+    ctx.check(rc)?;
+    Ok(sigs.chunks_exact(64).map(|c| eccoxide::protocol::ed25519::Signature::from_bytes(c.try_into().unwrap())).collect())
 }

@@ -55,6 +55,7 @@ pub const ECCX_PREP_CT_GATHER: u32 = 1 << 5;
 pub const ECCX_PREP_CT: u32 = 1 << 4; // ECCX_CT_SCAN: the secret-scalar fixed-base table / variable-base slabs
 pub const ECCX_PREP_ECDSA: u32 = 1 << 7; // eccx_ecdsa_verify's working slabs
 pub const ECCX_PREP_ED25519: u32 = 1 << 8; // eccx_ed25519_verify's working slab
+pub const ECCX_PREP_ED25519_SIGN: u32 = 1 << 9; // eccx_ed25519_sign's working slab, rows for 2 * max_n lanes
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -119,6 +120,16 @@ extern "C" {
     pub fn eccx_ed25519_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void,
                                    d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
                                    stream: *mut c_void) -> c_int;
+
+    // Ed25519 key derivation and signing, batched            SecretKey::public_key, SecretKey::sign, Keypair::sign
+    pub fn eccx_ed25519_public_key(ctx: *mut eccx_ctx, n: usize, seeds: *const u8, pubkeys: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_ed25519_public_key_dev(ctx: *mut eccx_ctx, n: usize, d_seeds: *const c_void, d_pubkeys: *mut c_void, opts: u32,
+                                       stream: *mut c_void) -> c_int;
+    pub fn eccx_ed25519_sign(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, seeds: *const u8,
+                             pubkeys: *const u8, sigs: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_ed25519_sign_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void,
+                                 d_seeds: *const c_void, d_pubkeys: *const c_void, d_sigs: *mut c_void, opts: u32,
+                                 stream: *mut c_void) -> c_int;
 
     // X25519 over a batch                                    protocol::x25519::x25519
     pub fn eccx_x25519(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,
