@@ -42,6 +42,10 @@ SYMBOLS = {
     "eccx_x25519_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_ecdsa_verify": (c_int, [c_void_p, c_int, c_size_t, _u8p, c_size_t, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_ecdsa_verify_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_ecdsa_sign": (c_int, [c_void_p, c_int, c_size_t, _u8p, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_ecdsa_sign_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_ecdsa_public_key": (c_int, [c_void_p, c_int, c_size_t, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_ecdsa_public_key_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_ed25519_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_ed25519_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_ed25519_public_key": (c_int, [c_void_p, c_size_t, _u8p, _u8p, c_uint32]),

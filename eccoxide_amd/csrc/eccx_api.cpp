@@ -78,6 +78,9 @@ struct eccx_ctx {
   // the same for eccx_ed25519_sign_dev / eccx_ed25519_public_key_dev (the comb's scalars r and a, its x || y and flags)
   uint8_t* edsign = nullptr;
   size_t edsign_cap = 0;
+  // the same for eccx_ecdsa_sign_dev / eccx_ecdsa_public_key_dev (the comb's x or x || y and flags)
+  uint8_t* ecsign = nullptr;
+  size_t ecsign_cap = 0;
   static constexpr int NEV = 10;
   hipEvent_t evs[NEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::mutex err_mu;       // err is written by whichever host thread's call failed last
@@ -227,6 +230,20 @@ int ensure_ed_sign(eccx_ctx* ctx, size_t n, EdSignSlab* out) {
   out->scal = ctx->edsign;
   out->pts = out->scal + align16(2 * n * 32);
   out->lflags = out->pts + align16(2 * n * 64);
+  return ECCX_OK;
+}
+
+// the ECDSA signing slab: the comb's output (x alone when signing; x || y before the SEC1 compressor when keys are
+// derived, n x 2FB) and the normalisation's flags (n)
+struct EcdsaSignSlab {
+  uint8_t *pts, *lflags;
+};
+size_t ecdsa_sign_slab_bytes(const CurveOps* ops, size_t n) { return align16(n * 2 * (size_t)ops->info.fb) + n; }
+int ensure_ecdsa_sign(eccx_ctx* ctx, const CurveOps* ops, size_t n, EcdsaSignSlab* out) {
+  const int rc = grow_slab(ctx, &ctx->ecsign, &ctx->ecsign_cap, ecdsa_sign_slab_bytes(ops, n));
+  if (rc || !out) return rc;
+  out->pts = ctx->ecsign;
+  out->lflags = out->pts + align16(n * 2 * (size_t)ops->info.fb);
   return ECCX_OK;
 }
 
@@ -765,6 +782,7 @@ void eccx_shutdown(eccx_ctx* ctx) {
   if (ctx->ecdsa) (void)hipFree(ctx->ecdsa);
   if (ctx->ed) (void)hipFree(ctx->ed);
   if (ctx->edsign) (void)hipFree(ctx->edsign);
+  if (ctx->ecsign) (void)hipFree(ctx->ecsign);
   for (auto& e : ctx->evs)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -871,6 +889,10 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     if (!rc) rc = ensure_ed_sign(ctx, max_n, nullptr);
     if (rc) return rc;
   }
+  if ((what & ECCX_PREP_ECDSA_SIGN) && ops->ecdsa_sign_finish) {  // eccx_ecdsa_sign's / _public_key's (the rows are sized above)
+    rc = ensure_ecdsa_sign(ctx, ops, max_n, nullptr);
+    if (rc) return rc;
+  }
   // slab of the reference-mirroring ladder (also what ECCX_CT_SCAN runs on a curve without a scanning fast ladder)
   const bool mirror_slab = (what & ECCX_PREP_MIRROR) || ((what & ECCX_PREP_CT) && !ops->var_ct);
   if (mirror_slab && ops->info.row_words) {
@@ -888,7 +910,8 @@ size_t eccx_device_bytes(const eccx_ctx* ctx) {
   std::lock_guard<std::mutex> g2(c->scratch_mu);
   size_t io = 0;
   for (size_t b : c->io_cap) io += b;
-  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap + c->ed_cap + c->edsign_cap;
+  return c->table_bytes + (c->scratch_words + c->jac_words) * sizeof(uint32_t) + io + c->ecdsa_cap + c->ed_cap + c->edsign_cap +
+         c->ecsign_cap;
 }
 
 int eccx_scalarmul_var_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points,
@@ -1252,6 +1275,150 @@ int eccx_ecdsa_verify(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests
     return eccx_ecdsa_verify_dev(ctx, curve, cnt, d_d + lo * db, digest_bytes, d_s + lo * 2 * sb, d_k + lo * kb, d_v + lo, opts,
                                  ctx->stream);
   });
+}
+
+// eccx_ecdsa_sign / _public_key[_dev]: everything checkable before a device is touched.  opts is 0 or ECCX_CT_GATHER
+// (ECCX_CT_SCAN is implied, not named); key derivation also takes ECCX_PUBKEY_SEC1.
+static int ecdsa_sign_args(eccx_ctx* ctx, const CurveOps* ops, size_t digest_bytes, uint32_t opts, bool keys) {
+  if (!ops->ecdsa_sign_finish || !ops->ecdsa_pubkey_finish || !ops->base_ct || !ops->to_affine_x)
+    return arg_err(ctx, keys ? "eccx_ecdsa_public_key: ECDSA is defined on p256r1, p384r1, p521r1 and p256k1"
+                             : "eccx_ecdsa_sign: ECDSA is defined on p256r1, p384r1, p521r1 and p256k1");
+  if (keys) {
+    if (opts & ~(uint32_t)(ECCX_CT_GATHER | ECCX_PUBKEY_SEC1))
+      return arg_err(ctx, "eccx_ecdsa_public_key: opts must be 0, ECCX_CT_GATHER and / or ECCX_PUBKEY_SEC1");
+  } else {
+    if (opts & ~(uint32_t)ECCX_CT_GATHER) return arg_err(ctx, "eccx_ecdsa_sign: opts must be 0 or ECCX_CT_GATHER");
+    if (digest_bytes > 2 * (size_t)ops->info.sb) return arg_err(ctx, "eccx_ecdsa_sign: digest_bytes must be 0 .. 2*SB");
+  }
+  return ECCX_OK;
+}
+
+// [scalars]G on the secret-scalar comb, normalised into d_out: x alone (FB bytes per unit) or x || y
+static int ecdsa_comb_ct(eccx_ctx* ctx, int curve, const CurveOps* ops, size_t n, const uint8_t* d_scalars, uint8_t* d_out,
+                         uint8_t* d_flags, bool gather, bool x_only, hipStream_t s) {
+  gather = gather && ops->base_ctg;
+  int rc = ensure_comb_ct(ctx, curve, ops, s, gather);
+  if (!rc) rc = ensure_rows(ctx, ops, n);
+  if (rc) return rc;
+  const size_t need = (n + eccx::LAUNCH_WG - 1) / eccx::LAUNCH_WG;
+  const int cgrid = (int)std::max<size_t>(1, std::min(need, (size_t)ctx->cus * 16));
+  HIP_TRY(ctx, (gather ? ops->base_ctg : ops->base_ct)(cgrid, s, n, d_scalars, gather ? ctx->comb_ctg[curve] : ctx->comb_ct[curve],
+                                                       ctx->jac, d_flags));
+  HIP_TRY(ctx, (x_only ? ops->to_affine_x : ops->to_affine_var)(norm_grid(ctx, n), s, n, ctx->jac, d_out, d_flags));
+  return ECCX_OK;
+}
+
+int eccx_ecdsa_sign_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_digests, size_t digest_bytes, const void* d_secrets,
+                        const void* d_nonces, void* d_sigs, void* d_status, uint32_t opts, void* stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ctx) return ECCX_ERR_ARG;
+  if (!ops) return curve_err(ctx);
+  int rc = ecdsa_sign_args(ctx, ops, digest_bytes, opts, false);
+  if (rc) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!d_digests || !d_secrets || !d_nonces || !d_sigs || !d_status) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EcdsaSignSlab w;
+  rc = ensure_ecdsa_sign(ctx, ops, n, &w);
+  if (rc) return rc;
+  // R = [k]G from the nonce rows as they are; its x-coordinate alone
+  rc = ecdsa_comb_ct(ctx, curve, ops, n, static_cast<const uint8_t*>(d_nonces), w.pts, w.lflags, (opts & ECCX_CT_GATHER) != 0, true, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, ops->ecdsa_sign_finish(flat_grid(ctx, n), s, n, static_cast<const uint8_t*>(d_digests), (int)digest_bytes,
+                                      static_cast<const uint8_t*>(d_secrets), static_cast<const uint8_t*>(d_nonces), w.pts, w.lflags,
+                                      static_cast<uint8_t*>(d_sigs), static_cast<uint8_t*>(d_status)));
+  return ECCX_OK;
+}
+
+// the device-side copies of secret inputs do not outlive a host call
+static int wipe_io(eccx_ctx* ctx, int rc, uint8_t* a, size_t a_bytes, uint8_t* b, size_t b_bytes) {
+  const hipError_t e1 = hipMemsetAsync(a, 0, a_bytes, ctx->stream);
+  const hipError_t e2 = b ? hipMemsetAsync(b, 0, b_bytes, ctx->stream) : hipSuccess;
+  const hipError_t e3 = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e1);
+  HIP_TRY(ctx, e2);
+  HIP_TRY(ctx, e3);
+  return ECCX_OK;
+}
+
+int eccx_ecdsa_sign(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests, size_t digest_bytes, const uint8_t* secrets,
+                    const uint8_t* nonces, uint8_t* sigs, uint8_t* status, uint32_t opts) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ctx) return ECCX_ERR_ARG;
+  if (!ops) return curve_err(ctx);
+  int rc = ecdsa_sign_args(ctx, ops, digest_bytes, opts, false);
+  if (rc) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!digests || !secrets || !nonces || !sigs || !status) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t sb = (size_t)ops->info.sb, db = digest_bytes ? digest_bytes : sb;
+  uint8_t *d_d = nullptr, *d_s = nullptr, *d_k = nullptr, *d_g = nullptr, *d_f = nullptr;
+  rc = ensure_io(ctx, IO_K, n * db, &d_d);
+  if (!rc) rc = ensure_io(ctx, IO_P, n * sb, &d_s);
+  if (!rc) rc = ensure_io(ctx, IO_J, n * sb, &d_k);
+  if (!rc) rc = ensure_io(ctx, IO_O, n * 2 * sb, &d_g);
+  if (!rc) rc = ensure_io(ctx, IO_F, n, &d_f);
+  if (rc) return rc;
+  const HostIn ins[3] = {{d_d, digests, db}, {d_s, secrets, sb}, {d_k, nonces, sb}};
+  const HostOut outs[2] = {{sigs, d_g, 2 * sb}, {status, d_f, 1}};
+  rc = host_pipeline(ctx, n, ins, 3, outs, 2, /*chunked=*/true, [&](size_t lo, size_t cnt) {
+    return eccx_ecdsa_sign_dev(ctx, curve, cnt, d_d + lo * db, digest_bytes, d_s + lo * sb, d_k + lo * sb, d_g + lo * 2 * sb, d_f + lo,
+                               opts, ctx->stream);
+  });
+  return wipe_io(ctx, rc, d_s, n * sb, d_k, n * sb);
+}
+
+int eccx_ecdsa_public_key_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_secrets, void* d_pubkeys, void* d_status,
+                              uint32_t opts, void* stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ctx) return ECCX_ERR_ARG;
+  if (!ops) return curve_err(ctx);
+  int rc = ecdsa_sign_args(ctx, ops, 0, opts, true);
+  if (rc) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!d_secrets || !d_pubkeys || !d_status) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EcdsaSignSlab w;
+  rc = ensure_ecdsa_sign(ctx, ops, n, &w);
+  if (rc) return rc;
+  const bool sec1 = (opts & ECCX_PUBKEY_SEC1) != 0;
+  const uint8_t* secrets = static_cast<const uint8_t*>(d_secrets);
+  uint8_t* keys = static_cast<uint8_t*>(d_pubkeys);
+  // Q = [d]G; x || y straight into the caller's buffer, or into the slab in front of the SEC1 compressor
+  rc = ecdsa_comb_ct(ctx, curve, ops, n, secrets, sec1 ? w.pts : keys, w.lflags, (opts & ECCX_CT_GATHER) != 0, false, s);
+  if (rc) return rc;
+  if (sec1) HIP_TRY(ctx, ops->compress(flat_grid(ctx, n), s, n, w.pts, w.lflags, keys));
+  HIP_TRY(ctx, ops->ecdsa_pubkey_finish(flat_grid(ctx, n), s, n, secrets, w.lflags, keys, sec1 ? ops->enc_bytes : 2 * ops->info.fb,
+                                        static_cast<uint8_t*>(d_status)));
+  return ECCX_OK;
+}
+
+int eccx_ecdsa_public_key(eccx_ctx* ctx, int curve, size_t n, const uint8_t* secrets, uint8_t* pubkeys, uint8_t* status,
+                          uint32_t opts) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ctx) return ECCX_ERR_ARG;
+  if (!ops) return curve_err(ctx);
+  int rc = ecdsa_sign_args(ctx, ops, 0, opts, true);
+  if (rc) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!secrets || !pubkeys || !status) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t sb = (size_t)ops->info.sb;
+  const size_t kb = (opts & ECCX_PUBKEY_SEC1) ? (size_t)ops->enc_bytes : 2 * (size_t)ops->info.fb;
+  uint8_t *d_s = nullptr, *d_q = nullptr, *d_f = nullptr;
+  rc = ensure_io(ctx, IO_P, n * sb, &d_s);
+  if (!rc) rc = ensure_io(ctx, IO_O, n * kb, &d_q);
+  if (!rc) rc = ensure_io(ctx, IO_F, n, &d_f);
+  if (rc) return rc;
+  const HostIn ins[1] = {{d_s, secrets, sb}};
+  const HostOut outs[2] = {{pubkeys, d_q, kb}, {status, d_f, 1}};
+  rc = host_pipeline(ctx, n, ins, 1, outs, 2, /*chunked=*/true, [&](size_t lo, size_t cnt) {
+    return eccx_ecdsa_public_key_dev(ctx, curve, cnt, d_s + lo * sb, d_q + lo * kb, d_f + lo, opts, ctx->stream);
+  });
+  return wipe_io(ctx, rc, d_s, n * sb, nullptr, 0);
 }
 
 int eccx_ed25519_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_sigs,

@@ -8,12 +8,14 @@
 //   ECCX_GLV_PARAMS  (optional) the curve's endomorphism constants: instantiates the GLV form of the
 //                    affine-table ladder (kernels_coz.hpp) beside the plain one
 //   ECCX_ORDER       (optional) the struct of the group order n (curve_consts.inc, e.g. P256_ORD): instantiates the
-//                    ECDSA verification passes (kernels_ecdsa.hpp)
+//                    ECDSA verification passes (kernels_ecdsa.hpp) and the passes that finish signing and key derivation
+//                    (kernels_ecdsa_sign.hpp)
 #include "kernels_codec.hpp"
 #include "kernels_coz.hpp"
 #include "launch.hpp"
 #ifdef ECCX_ORDER
 #include "kernels_ecdsa.hpp"
+#include "kernels_ecdsa_sign.hpp"
 #endif
 #ifndef ECCX_CODEC_FORMAT
 #define ECCX_CODEC_FORMAT FORMAT_SEC1
@@ -218,6 +220,18 @@ hipError_t ecdsa_finish_(int grid, hipStream_t s, size_t n, const uint8_t* sigs,
   hipLaunchKernelGGL(k_ecdsa_finish<ECCX_ORDER>, dim3(grid), dim3(WG), 0, s, n, sigs, xs, lflags, verdicts);
   return hipGetLastError();
 }
+// ECDSA signing and key derivation (kernels_ecdsa_sign.hpp): the passes behind the secret-scalar comb
+hipError_t ecdsa_sign_finish_(int grid, hipStream_t s, size_t n, const uint8_t* digests, int digest_bytes, const uint8_t* secrets,
+                              const uint8_t* nonces, const uint8_t* xs, const uint8_t* lflags, uint8_t* sigs, uint8_t* status) {
+  hipLaunchKernelGGL(k_ecdsa_sign_finish<ECCX_ORDER>, dim3(grid), dim3(WG), 0, s, n, digests, digest_bytes, secrets, nonces, xs, lflags,
+                     sigs, status);
+  return hipGetLastError();
+}
+hipError_t ecdsa_pubkey_finish_(int grid, hipStream_t s, size_t n, const uint8_t* secrets, const uint8_t* lflags, uint8_t* out, int width,
+                                uint8_t* status) {
+  hipLaunchKernelGGL(k_ecdsa_pubkey_finish<ECCX_ORDER>, dim3(grid), dim3(WG), 0, s, n, secrets, lflags, out, width, status);
+  return hipGetLastError();
+}
 #endif
 }  // namespace
 const CurveOps& ECCX_OPS_NAME() {
@@ -251,6 +265,8 @@ const CurveOps& ECCX_OPS_NAME() {
 #ifdef ECCX_ORDER
     t.ecdsa_prepare = ecdsa_prepare_;
     t.ecdsa_finish = ecdsa_finish_;
+    t.ecdsa_sign_finish = ecdsa_sign_finish_;
+    t.ecdsa_pubkey_finish = ecdsa_pubkey_finish_;
 #endif
 #ifdef ECCX_EXTRA_OPS
     ECCX_EXTRA_OPS(t);

@@ -149,6 +149,15 @@ struct CurveOps {
   hipError_t (*ed_sign_finish)(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* pubkeys,
                                const uint8_t* pts, uint8_t* scal, uint8_t* sigs);
   hipError_t (*ed_pubkey_finish)(int grid, hipStream_t s, size_t n, const uint8_t* pts, uint8_t* scal, uint8_t* out);
+  // ECDSA signing and key derivation (kernels_ecdsa_sign.hpp; null where the curve has no ECDSA), behind the secret-scalar
+  // comb.  ecdsa_sign_finish takes the digests as ecdsa_prepare does, the secrets and nonces (SB bytes each), the
+  // x-coordinates of [k]G (FB bytes) with the normalisation's flags, and writes r || s and a status byte per unit (zeros
+  // where the signature is refused).  ecdsa_pubkey_finish tests the secrets' range and zeroes the refused units' records
+  // of `width` bytes in `out`.
+  hipError_t (*ecdsa_sign_finish)(int grid, hipStream_t s, size_t n, const uint8_t* digests, int digest_bytes, const uint8_t* secrets,
+                                  const uint8_t* nonces, const uint8_t* xs, const uint8_t* lflags, uint8_t* sigs, uint8_t* status);
+  hipError_t (*ecdsa_pubkey_finish)(int grid, hipStream_t s, size_t n, const uint8_t* secrets, const uint8_t* lflags, uint8_t* out,
+                                    int width, uint8_t* status);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above

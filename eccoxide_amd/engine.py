@@ -31,9 +31,12 @@ PREP_VAR, PREP_BASE, PREP_BASE_LDS, PREP_MIRROR, PREP_CT, PREP_CT_GATHER, PREP_H
 PREP_ECDSA = 128
 PREP_ED25519 = 256
 PREP_ED25519_SIGN = 512
+PREP_ECDSA_SIGN = 1024
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
 SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
+# status bytes of ecdsa_sign / ecdsa_public_key (include/eccx.h: ECCX_SIGN_*)
+SIGN_NONE, SIGN_OK = 0, 1
 ECDSA_CURVES = (P256R1, P384R1, P521R1, P256K1)
 
 
@@ -142,16 +145,17 @@ class Engine:
                                            | (PREP_CT if ct else 0) | (PREP_CT_GATHER if ct_gather else 0)))
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
-                ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False):
+                ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
-        row buffer for 2 * max_n lanes."""
+        row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
                                            | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)
-                                           | (PREP_ED25519_SIGN if ed25519_sign else 0)))
+                                           | (PREP_ED25519_SIGN if ed25519_sign else 0)
+                                           | (PREP_ECDSA_SIGN if ecdsa_sign else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -291,6 +295,90 @@ class Engine:
                                                     pubkeys.data_ptr(), verdicts.data_ptr(), PUBKEY_SEC1 if sec1 else 0,
                                                     stream))
         return verdicts
+
+    def ecdsa_sign(self, curve, digests: bytes, secrets: bytes, nonces: bytes, *, digest_bytes: Optional[int] = None,
+                   ct_gather: bool = False):
+        """ECDSA signatures of a batch (eccx_ecdsa_sign; src/protocol/ecdsa.rs sign / sign_hashed) with the caller's
+        nonces, as in the reference: a nonce that repeats or can be predicted gives the key away.  digests as in
+        ecdsa_verify (digest_bytes=0: n x SB scalars used as they are); secrets, nonces: n x SB big-endian.  Returns
+        (sigs, status): n x 2SB r || s and n bytes, SIGN_OK or SIGN_NONE with a zero record (d or k zero or >= n, r = 0,
+        s = 0).  The secret-scalar comb always runs; ct_gather selects its cross-lane lookup (ECCX_CT_GATHER)."""
+        cid, sb, _ = self._ecdsa_widths(curve, digest_bytes, False)
+        if len(secrets) % sb:
+            raise ValueError(f"secrets must be n x {sb} bytes")
+        n = len(secrets) // sb
+        if digest_bytes is None:
+            if n == 0 or len(digests) % n:
+                raise ValueError("cannot infer digest_bytes: give it explicitly")
+            digest_bytes = len(digests) // n
+        db = int(digest_bytes)
+        if len(digests) != n * (db or sb) or len(nonces) != n * sb:
+            raise ValueError(f"digests must be n x {db or sb} bytes and nonces n x {sb} bytes")
+        sigs = ctypes.create_string_buffer(max(1, 2 * sb * n))
+        status = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_ecdsa_sign(self._ctx, cid, n, digests, db, secrets, nonces, sigs, status,
+                                              CT_GATHER if ct_gather else 0))
+        return sigs.raw[:2 * sb * n], status.raw[:n]
+
+    def ecdsa_sign_t(self, curve, digests, secrets, nonces, sigs=None, status=None, *, digest_bytes: Optional[int] = None,
+                     ct_gather: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of ecdsa_sign (torch.uint8 CUDA tensors; eccx_ecdsa_sign_dev): enqueued on `stream`
+        (default: torch's current stream); returns the n x 2SB signature tensor and the n-byte status tensor."""
+        import torch
+
+        cid, sb, _ = self._ecdsa_widths(curve, digest_bytes, False)
+        n = self._units(secrets, sb, "secrets")
+        if digest_bytes is None:
+            if n == 0 or digests.numel() % n:
+                raise ValueError("cannot infer digest_bytes: give it explicitly")
+            digest_bytes = digests.numel() // n
+        db = int(digest_bytes)
+        if sigs is None:
+            sigs = torch.empty((n * 2 * sb,), dtype=torch.uint8, device=secrets.device)
+        if status is None:
+            status = torch.empty((n,), dtype=torch.uint8, device=secrets.device)
+        self._tensors(n, ("digests", digests, db or sb), ("secrets", secrets, sb), ("nonces", nonces, sb),
+                      ("sigs", sigs, 2 * sb), ("status", status, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(secrets.device).cuda_stream
+        self._check(self._lib.eccx_ecdsa_sign_dev(self._ctx, cid, n, digests.data_ptr(), db, secrets.data_ptr(),
+                                                  nonces.data_ptr(), sigs.data_ptr(), status.data_ptr(),
+                                                  CT_GATHER if ct_gather else 0, stream))
+        return sigs, status
+
+    def ecdsa_public_key(self, curve, secrets: bytes, *, sec1: bool = False, ct_gather: bool = False):
+        """ECDSA public keys Q = [d]G of a batch of secrets (eccx_ecdsa_public_key; ecdsa::public_key): secrets n x SB
+        big-endian.  Returns (pubkeys, status): n x 2FB affine x || y, or n x (FB + 1) SEC1 compressed with sec1=True, and
+        n bytes, SIGN_OK or SIGN_NONE with a zero record (d zero or >= n)."""
+        cid, sb, kb = self._ecdsa_widths(curve, None, sec1)
+        if len(secrets) % sb:
+            raise ValueError(f"secrets must be n x {sb} bytes")
+        n = len(secrets) // sb
+        keys = ctypes.create_string_buffer(max(1, kb * n))
+        status = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_ecdsa_public_key(self._ctx, cid, n, secrets, keys, status,
+                                                    (PUBKEY_SEC1 if sec1 else 0) | (CT_GATHER if ct_gather else 0)))
+        return keys.raw[:kb * n], status.raw[:n]
+
+    def ecdsa_public_key_t(self, curve, secrets, pubkeys=None, status=None, *, sec1: bool = False, ct_gather: bool = False,
+                           stream: Optional[int] = None):
+        """Device-tensor form of ecdsa_public_key (eccx_ecdsa_public_key_dev): enqueued on `stream` (default: torch's
+        current stream); returns the key tensor and the n-byte status tensor."""
+        import torch
+
+        cid, sb, kb = self._ecdsa_widths(curve, None, sec1)
+        n = self._units(secrets, sb, "secrets")
+        if pubkeys is None:
+            pubkeys = torch.empty((n * kb,), dtype=torch.uint8, device=secrets.device)
+        if status is None:
+            status = torch.empty((n,), dtype=torch.uint8, device=secrets.device)
+        self._tensors(n, ("secrets", secrets, sb), ("pubkeys", pubkeys, kb), ("status", status, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(secrets.device).cuda_stream
+        self._check(self._lib.eccx_ecdsa_public_key_dev(self._ctx, cid, n, secrets.data_ptr(), pubkeys.data_ptr(),
+                                                        status.data_ptr(),
+                                                        (PUBKEY_SEC1 if sec1 else 0) | (CT_GATHER if ct_gather else 0), stream))
+        return pubkeys, status
 
     def ed25519_verify(self, messages, sigs: bytes, pubkeys: bytes) -> bytes:
         """Ed25519 verification of a batch (eccx_ed25519_verify; src/protocol/ed25519.rs verify): messages is a list of

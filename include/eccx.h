@@ -20,6 +20,7 @@
  *   eccx_point_add[_dev]       impl Add / Sub / Neg, CurveGroup::double   curve_macros.rs:297-411, group.rs:28-70
  *   eccx_double_scalarmul[_dev]  u1*G + u2*Q                     src/protocol/ecdsa.rs:215, ed25519.rs:145
  *   eccx_ecdsa_verify[_dev]      ECDSA verification              src/protocol/ecdsa.rs:200-222
+ *   eccx_ecdsa_public_key[_dev], eccx_ecdsa_sign[_dev]  ecdsa::public_key, sign_hashed / sign  src/protocol/ecdsa.rs:146-198
  *   eccx_ed25519_verify[_dev]    Ed25519 verification            src/protocol/ed25519.rs:119-146
  *   eccx_ed25519_public_key[_dev]  SecretKey::public_key        src/protocol/ed25519.rs:62-80, 175-190
  *   eccx_ed25519_sign[_dev]      SecretKey::sign / Keypair::sign   src/protocol/ed25519.rs:91-117, 192-247
@@ -199,6 +200,8 @@ enum {
                                    the ladder's output and flags) and the slabs of the verify-shape ladder it runs */
   ECCX_PREP_ED25519_SIGN = 1u << 9, /* eccx_reserve (edwards25519): the working slab of eccx_ed25519_sign / _public_key (the
                                    comb's scalars, its output and flags) and the fixed-base row buffer, for 2 * max_n lanes */
+  ECCX_PREP_ECDSA_SIGN = 1u << 10, /* eccx_reserve: the working slab of eccx_ecdsa_sign / eccx_ecdsa_public_key (the comb's
+                                   output and flags) and the fixed-base row buffer */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -218,6 +221,13 @@ enum {
                              decrease */
   ECCX_SIG_BAD_KEY = 3    /* ECDSA: the public key is non-canonical, off the curve or the identity, or its SEC1 bytes do
                              not decode.  Ed25519: A fails decode_point (small and mixed order keys are legal) */
+};
+
+/* eccx_ecdsa_sign / eccx_ecdsa_public_key: one status byte per unit */
+enum {
+  ECCX_SIGN_NONE = 0, /* the reference's CtOption is not present: d or k is 0 or >= n, r = 0, s = 0, or a digest_bytes == 0
+                         scalar is >= n; the unit's output is zero bytes */
+  ECCX_SIGN_OK = 1
 };
 
 typedef struct eccx_ctx eccx_ctx;
@@ -322,6 +332,39 @@ int eccx_ecdsa_verify(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests
                       const uint8_t* sigs, const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts);
 int eccx_ecdsa_verify_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_digests, size_t digest_bytes,
                           const void* d_sigs, const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream);
+
+/* ECDSA signing and public-key derivation, batched (src/protocol/ecdsa.rs public_key, :146-149; sign_hashed / sign,
+ * :165-198).  The nonce is an argument, as in the reference (:56-64: "This module takes the nonce as a parameter and does
+ * not generate it"): a nonce that repeats, or that an observer can predict, gives the secret key away.
+ *   curves  : p256r1, p384r1, p521r1, p256k1 (others: ECCX_ERR_ARG)
+ *   digests, digest_bytes : as in eccx_ecdsa_verify (0 .. 2*SB, bits2int; 0: n x SB scalars z used as they are,
+ *             sign_hashed, z >= n gives ECCX_SIGN_NONE)
+ *   secrets, nonces : n x SB big-endian, d and k
+ *   sigs    : n x 2*SB, r || s big-endian (Signature::to_bytes).  Low-S is not applied, as in the reference.
+ *   pubkeys : n x 2*FB affine x || y, or n x (FB + 1) SEC1 compressed with ECCX_PUBKEY_SEC1
+ *   status  : n bytes.  ECCX_SIGN_OK where the reference's CtOption is present; ECCX_SIGN_NONE, with the unit's sigs or
+ *             pubkeys record all zero bytes, where it is not: d = 0, k = 0, r = 0, s = 0, and equally d or k >= n
+ *             (Scalar::from_slice_be would have refused it).  The other units stand.
+ * On the GPU: R = [k]G (Q = [d]G) on the secret-scalar fixed-base comb of eccx_scalarmul_base, read straight from the
+ * caller's rows (ECCX_CT_SCAN is implied; the default comb never runs), the select-only normalisation (x alone when
+ * signing), and ONE pass with r = x mod n, the range tests of d and k, k' = k or 1, w = k'^-1 by division steps modulo n,
+ * s = w (z + r d) and the validity fold.  d, k, k', w, r d and z + r d steer no branch and no memory address (SIDE
+ * CHANNELS above; profiles/ecdsa_sign_isa_ct.txt), and no value derived from them but the signature is written to
+ * device memory: that pass has no stack frame, no register spills to scratch memory and no LDS (the same census; the
+ * inverse is inlined into it for this reason).  The digest, z, r, s and the status are public.
+ * opts: 0, or ECCX_CT_GATHER for the cross-lane lookup under that option's caveat; eccx_ecdsa_public_key also takes
+ * ECCX_PUBKEY_SEC1; anything else is ECCX_ERR_ARG.  n == 0 returns ECCX_OK whatever the pointers.
+ * The host forms clear their device-side copies of the secrets and nonces before returning.  The _dev forms enqueue on
+ * `stream` without synchronising and use the context's signing slab (grow-only; eccx_reserve with ECCX_PREP_ECDSA_SIGN
+ * sizes it, eccx_prepare with ECCX_PREP_CT / ECCX_PREP_CT_GATHER builds the table). */
+int eccx_ecdsa_sign(eccx_ctx* ctx, int curve, size_t n, const uint8_t* digests, size_t digest_bytes, const uint8_t* secrets,
+                    const uint8_t* nonces, uint8_t* sigs, uint8_t* status, uint32_t opts);
+int eccx_ecdsa_sign_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_digests, size_t digest_bytes, const void* d_secrets,
+                        const void* d_nonces, void* d_sigs, void* d_status, uint32_t opts, void* stream);
+int eccx_ecdsa_public_key(eccx_ctx* ctx, int curve, size_t n, const uint8_t* secrets, uint8_t* pubkeys, uint8_t* status,
+                          uint32_t opts);
+int eccx_ecdsa_public_key_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_secrets, void* d_pubkeys, void* d_status,
+                              uint32_t opts, void* stream);
 
 /* Ed25519 verification, batched (src/protocol/ed25519.rs verify, :119-146; PureEdDSA, RFC 8032 §5.1.7 as the
  * reference implements it: cofactorless, [S]B == R + [k]A).

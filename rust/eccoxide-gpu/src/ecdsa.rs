@@ -1,7 +1,9 @@
 //! Batched ECDSA verification (`src/protocol/ecdsa.rs` `verify` / `verify_hashed`, `:200-222`) for the four curves
 //! the library serves: one call into `libeccx.so` per batch (`eccx_ecdsa_verify`), which checks the signature
 //! components, converts the digests (`digest_to_scalar`), inverts `s` modulo the order, runs `u1*G + u2*Q` and
-//! compares `x mod n` with `r` on the GPU.
+//! compares `x mod n` with `r` on the GPU.  Signing and key derivation (`sign` / `sign_hashed`, `:165-198`;
+//! `public_key`, `:146-149`) likewise: `eccx_ecdsa_sign` and `eccx_ecdsa_public_key` on the secret-scalar kernels, with
+//! the caller's nonces as in the reference.
 //!
 //! The reference's `verify` takes a message and hashes it; here the caller hands the digests its hash function
 //! produced (any SHA-2 size: the library applies `bits2int`).  A `Point` is a valid key by construction in the
@@ -43,7 +45,7 @@ pub(crate) fn verdict_of(b: u8) -> Verdict {
 macro_rules! gpu_ecdsa_curve {
     ($modname:ident, $($seg:ident)::+, $id:expr, $fb:expr, $sb:expr) => {
         pub mod $modname {
-            use $($seg)::+::{Point, Scalar};
+            use $($seg)::+::{FieldElement, Point, PointAffine, Scalar};
             use eccoxide::protocol::ecdsa::Signature;
 
             use super::Verdict;
@@ -99,6 +101,91 @@ macro_rules! gpu_ecdsa_curve {
                     d.extend_from_slice(&z.to_bytes());
                 }
                 run(ctx, public, &d, 0, sigs)
+            }
+
+            fn run_sign(ctx: &GpuContext, secret: &[Scalar], nonce: &[Scalar], digests: &[u8], digest_bytes: usize, gather: bool)
+                        -> Result<Vec<Option<Signature<Scalar>>>, GpuError> {
+                assert_eq!(secret.len(), nonce.len());
+                let n = secret.len();
+                let (mut d, mut k) = (Vec::with_capacity(n * SB), Vec::with_capacity(n * SB));
+                for i in 0..n {
+                    d.extend_from_slice(&secret[i].to_bytes());
+                    k.extend_from_slice(&nonce[i].to_bytes());
+                }
+                let (mut sigs, mut status) = (vec![0u8; n * 2 * SB], vec![0u8; n]);
+                let rc = unsafe {
+                    ffi::eccx_ecdsa_sign(ctx.raw(), $id, n, digests.as_ptr(), digest_bytes, d.as_ptr(), k.as_ptr(),
+                                         sigs.as_mut_ptr(), status.as_mut_ptr(), if gather { ffi::ECCX_CT_GATHER } else { 0 })
+                };
+                for b in &mut d {
+                    *b = 0; // the host-side copies of the secrets and nonces do not outlive the call
+                }
+                for b in &mut k {
+                    *b = 0;
+                }
+                ctx.check(rc)?;
+                Ok((0..n)
+                    .map(|i| {
+                        if status[i] != ffi::ECCX_SIGN_OK {
+                            return None; // the reference's CtOption is not present
+                        }
+                        let rec = &sigs[i * 2 * SB..(i + 1) * 2 * SB];
+                        let r = Scalar::from_bytes(rec[..SB].try_into().unwrap())?;
+                        let s = Scalar::from_bytes(rec[SB..].try_into().unwrap())?;
+                        Signature::from_scalars(r, s)
+                    })
+                    .collect())
+            }
+
+            /// `sign(&secret[i], &nonce[i], message_i)` where `digests[i]` is the digest of message `i` under the scheme's
+            /// hash function (`N` bytes, at most `2 * SB`); `None` where the reference's `CtOption` is not present.  The
+            /// nonces are the caller's, as in the reference: unique and unpredictable, or the key is lost.  `gather`
+            /// selects the cross-lane lookup (`ECCX_CT_GATHER`, see `eccx.h`).
+            pub fn sign_batch<const N: usize>(ctx: &GpuContext, secret: &[Scalar], nonce: &[Scalar], digests: &[[u8; N]],
+                                              gather: bool) -> Result<Vec<Option<Signature<Scalar>>>, GpuError> {
+                assert_eq!(digests.len(), secret.len());
+                let d: Vec<u8> = digests.iter().flatten().copied().collect();
+                run_sign(ctx, secret, nonce, &d, N, gather)
+            }
+
+            /// `sign_hashed(&secret[i], &nonce[i], hashed[i])`.
+            pub fn sign_hashed_batch(ctx: &GpuContext, secret: &[Scalar], nonce: &[Scalar], hashed: &[Scalar], gather: bool)
+                                     -> Result<Vec<Option<Signature<Scalar>>>, GpuError> {
+                assert_eq!(hashed.len(), secret.len());
+                let mut d = Vec::with_capacity(hashed.len() * SB);
+                for z in hashed {
+                    d.extend_from_slice(&z.to_bytes());
+                }
+                run_sign(ctx, secret, nonce, &d, 0, gather)
+            }
+
+            /// `public_key(&secret[i])` in affine form; `None` for a zero secret (the identity has no affine form).
+            pub fn public_keys_batch(ctx: &GpuContext, secret: &[Scalar], gather: bool) -> Result<Vec<Option<PointAffine>>, GpuError> {
+                let n = secret.len();
+                let mut d = Vec::with_capacity(n * SB);
+                for s in secret {
+                    d.extend_from_slice(&s.to_bytes());
+                }
+                let (mut keys, mut status) = (vec![0u8; n * 2 * FB], vec![0u8; n]);
+                let rc = unsafe {
+                    ffi::eccx_ecdsa_public_key(ctx.raw(), $id, n, d.as_ptr(), keys.as_mut_ptr(), status.as_mut_ptr(),
+                                               if gather { ffi::ECCX_CT_GATHER } else { 0 })
+                };
+                for b in &mut d {
+                    *b = 0;
+                }
+                ctx.check(rc)?;
+                Ok((0..n)
+                    .map(|i| {
+                        if status[i] != ffi::ECCX_SIGN_OK {
+                            return None;
+                        }
+                        let rec = &keys[i * 2 * FB..(i + 1) * 2 * FB];
+                        let x = FieldElement::from_bytes(rec[..FB].try_into().unwrap())?;
+                        let y = FieldElement::from_bytes(rec[FB..].try_into().unwrap())?;
+                        PointAffine::from_coordinate(&x, &y)
+                    })
+                    .collect())
             }
         }
     };

@@ -56,6 +56,7 @@ pub const ECCX_PREP_CT: u32 = 1 << 4; // ECCX_CT_SCAN: the secret-scalar fixed-b
 pub const ECCX_PREP_ECDSA: u32 = 1 << 7; // eccx_ecdsa_verify's working slabs
 pub const ECCX_PREP_ED25519: u32 = 1 << 8; // eccx_ed25519_verify's working slab
 pub const ECCX_PREP_ED25519_SIGN: u32 = 1 << 9; // eccx_ed25519_sign's working slab, rows for 2 * max_n lanes
+pub const ECCX_PREP_ECDSA_SIGN: u32 = 1 << 10; // eccx_ecdsa_sign's / eccx_ecdsa_public_key's working slab
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -67,6 +68,10 @@ pub const ECCX_SIG_INVALID: u8 = 0;
 pub const ECCX_SIG_VALID: u8 = 1;
 pub const ECCX_SIG_MALFORMED: u8 = 2;
 pub const ECCX_SIG_BAD_KEY: u8 = 3;
+
+// status bytes, one per unit (eccx_ecdsa_sign, eccx_ecdsa_public_key)
+pub const ECCX_SIGN_NONE: u8 = 0;
+pub const ECCX_SIGN_OK: u8 = 1;
 
 #[link(name = "eccx")]
 extern "C" {
@@ -113,6 +118,17 @@ extern "C" {
     pub fn eccx_ecdsa_verify_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_digests: *const c_void, digest_bytes: usize,
                                  d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
                                  stream: *mut c_void) -> c_int;
+
+    // ECDSA signing and key derivation, batched              protocol::ecdsa::sign_hashed / sign, public_key
+    pub fn eccx_ecdsa_sign(ctx: *mut eccx_ctx, curve: c_int, n: usize, digests: *const u8, digest_bytes: usize,
+                           secrets: *const u8, nonces: *const u8, sigs: *mut u8, status: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_ecdsa_sign_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_digests: *const c_void, digest_bytes: usize,
+                               d_secrets: *const c_void, d_nonces: *const c_void, d_sigs: *mut c_void, d_status: *mut c_void,
+                               opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_ecdsa_public_key(ctx: *mut eccx_ctx, curve: c_int, n: usize, secrets: *const u8, pubkeys: *mut u8,
+                                 status: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_ecdsa_public_key_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_secrets: *const c_void,
+                                     d_pubkeys: *mut c_void, d_status: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
 
     // Ed25519 verification, batched                         protocol::ed25519 verify (PublicKey::verify)
     pub fn eccx_ed25519_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, sigs: *const u8,
