@@ -7,9 +7,10 @@
 //   a = 0 (BLS12-381 G1)   the ladder runs on the isomorphic curve E': y^2 = x^3 + b zeta^6 on which
 //                          the rescaled entries are affine; Z *= zeta at the end.  No inversion.
 //   a = -3 (P-256/384/521) the doubling uses a, so the ladder stays on the curve: the common
-//                          denominator zeta = Z_16 is INVERTED once per unit (division steps,
-//                          inv_gcd.hpp: about 60 products' worth of issue slots) and folded into the
-//                          rescaling pass, which then yields true affine entries.
+//                          denominator zeta = Z_16 is INVERTED (division steps, inv_gcd.hpp: about 60
+//                          products' worth of issue slots; the public ladders: once per four units, shared
+//                          through LDS, SHARED_INV below) and folded into the rescaling pass,
+//                          which then yields true affine entries.
 // k_scalarmul_coz_unsat is launched in front of k_scalarmul_var_unsat, which redoes the (rare) units
 // this kernel marks as degenerate.
 #pragma once
@@ -239,7 +240,8 @@ ECCX_DEV void glv_split_lattice(uint32_t (&k1)[5], uint32_t (&k2)[5], uint32_t& 
 //   common Z      backward pass, per entry l *= ratio, l^2, l^3, X l^2, Y l^3 (4 products + 1 square);
 //                 l starts at 1 (a = 0: entries affine on E', zeta = Z_16 kept for the end) or at
 //                 1 / Z_16 (a = -3: entries affine on the curve itself)
-//   ladder        per signed 5-bit window 5 doublings + 1 mixed addition (2 with GLV)
+//   ladder        per signed 5-bit window 5 doublings + 1 mixed addition (2 with GLV); the public ladder without
+//                 endomorphism aligns the windows to the top, so that the short one is the last (S below)
 // GLV = true is the ECCX_ASSUME_SUBGROUP form (BLS12-381 bases in G1): k = k1 + k2 x^2, the second
 // half added from (beta x', -y') -- sigma commutes with the isomorphism.
 // A base point of order <= 16 makes the build degenerate (some T_d is the point at infinity or +-P,
@@ -459,6 +461,17 @@ constexpr int coz_occupancy() {
                     : (CU::N <= 14 ? (GLV ? ECCX_OCC_U14 : (CU::KIND == UK_MONT ? ECCX_COZ_OCC_BLS : ECCX_COZ_OCC_U14)) : ECCX_OCC_U18);
 }
 
+// The public a = -3 ladders invert ONE table denominator per lane column of the workgroup: a wave instruction costs the
+// same for one lane as for 64, so lanes cannot share an inversion, but the WG / 64 waves can, through LDS.  Every lane
+// leaves its zeta in LDS ([limb][thread]: conflict-free); per iteration of the grid-stride loop one wave, the duty wave,
+// multiplies the four values of threads c, 64 + c, 128 + c, 192 + c, inverts the product (fe_inv_gcd: 23 k of a
+// P-256 unit's 454 k vector instructions) and back-substitutes the four inverses: 9 products for 3 inversions saved.
+// The duty rotates over the iterations, so every wave inverts once in four (a rotation that also starts at another wave
+// in every workgroup measured no different: DESIGN.md 3.9).  The secret-scalar ladders keep one inversion per lane.
+// The public ladder without endomorphism aligns its windows to the TOP of the 8 SB + 1 Booth positions
+// (booth_digit_aligned): the short window -- S = (8 SB + 1) mod WB positions: P-256 2, P-384 0, P-521 4 -- is then the
+// bottom one, which costs S doublings, where a short top window costs the WB doublings below it all the same.
+
 // scratch: [workgroup][row 0..16][thread][urowc_words]; row 0: split scalar (words 0..15, GLV) and
 // zeta (words 16..16+N); rows 1..16: the table.
 // FUSED: the verify shape u1*G + u2*Q (u1*G - u2*Q with OPT_NEGATE_B; src/protocol/ecdsa.rs:215) in one pass, as in
@@ -489,6 +502,11 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
   constexpr int SB = CS::SB;
   static_assert(!GLV || SB == 32, "the split is written for 256-bit scalars");
   constexpr int NWIN = GLV ? (G::K_BITS + 1 + WB - 1) / WB : (8 * SB + 1 + WB - 1) / WB;
+  // windows aligned to the top: S scalar bits below the NWIN_MAIN full windows, added after S doublings at the very end
+  constexpr int S = (!GLV && !CT) ? (8 * SB + 1) % WB : 0;
+  constexpr int NWIN_MAIN = S != 0 ? (8 * SB + 1) / WB : NWIN;
+  constexpr bool SHARED_INV = !ISO && !CT;
+  static_assert(WG == 256, "the shared inversion multiplies the values of four waves");
   constexpr int WR = urowc_words<CU>();
   static_assert(!ISO || WR >= 16 + N, "row 0 holds the split scalar and zeta");
   using T = U<CU, 1, 3>;
@@ -502,7 +520,10 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
   static_assert(!CT || (size_t)TBL * WC <= (size_t)(FAST_TABLE_ROWS - 1 - TBL) * WR, "the compact table must fit the free rows");
   uint32_t* cslab = scratch + ((size_t)blockIdx.x * FAST_TABLE_ROWS + (TBL + 1)) * WG * (size_t)WR + (size_t)threadIdx.x * WC;
   auto crow = [&](uint32_t e) { return cslab + (size_t)(e - 1) * WG * WC; };
-  for (size_t base = (size_t)blockIdx.x * WG; base < n; base += (size_t)gridDim.x * WG) {
+  // iter: the shared inversion's duty rotation.  The loop bound is the same for the whole workgroup and a lane without a
+  // unit of its own computes the clamped one, so every lane reaches the barriers of every iteration.
+  uint32_t iter = 0u;
+  for (size_t base = (size_t)blockIdx.x * WG; base < n; base += (size_t)gridDim.x * WG, ++iter) {
     const size_t gid = base + threadIdx.x;
     const bool active = gid < n;
     const size_t idx = active ? gid : n - 1;
@@ -559,6 +580,8 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         d = (m >> 1) + (m & 1u);
         neg = (s & 1u) != 0;
         if constexpr (LATTICE) neg = neg != (h[5] != 0u);  // a negative half: -digit
+      } else if constexpr (S != 0) {
+        booth_digit_aligned<WB, SB, S>(k, w, d, neg);  // w = -1: the bottom digit
       } else {
         booth_digit<WB, SB>(k, w, d, neg);
       }
@@ -595,11 +618,61 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         if constexpr (CT) u2_store<CU, (ECCX_CT_VAR_PK != 0)>(crow(TBL), tx, ty);  // the top entry is affine on E' as it stands
         else if constexpr (GLV) u3_store<CU>(row(TBL), tx, ty, u_fit<1, 3>(u_mul_k<CU>(tx, CU::BETA)));
       } else {
-        // 1 / zeta (zeta = 0 only for degenerate units, which are redone anyway: the inverse of 0 is 0)
-        Fe<L> c;
-        u_to_canonical<CU>(c, zacc);
-        fe_inv_gcd<CS>(c, c);
-        lam = u_as<1, 3>(u_to_mont<CU>(c));
+        if constexpr (SHARED_INV) {
+          // 1 / zeta through the workgroup: zeta is the product of the ratios, zero exactly where `degenerate` is set;
+          // such a unit is redone anyway and enters the shared product as 1, so that its column's other lanes get
+          // their inverses
+          __shared__ uint32_t zsh[N][WG];
+          const uint32_t tid = threadIdx.x;
+          T zs;
+          u_select(zs, degenerate, one, zacc);
+#pragma unroll
+          for (int i = 0; i < N; ++i) zsh[i][tid] = zs.v[i];
+          __syncthreads();
+          if ((uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) == (iter & 3u)) {
+            const uint32_t col = tid & 63u;
+            auto get = [&](int j) {
+              T a;
+#pragma unroll
+              for (int i = 0; i < N; ++i) a.v[i] = zsh[i][col + 64u * j];
+              return a;
+            };
+            auto put = [&](int j, const T& a) {
+#pragma unroll
+              for (int i = 0; i < N; ++i) zsh[i][col + 64u * j] = a.v[i];
+            };
+            // prefix products p1 = a0 a1, p2 = p1 a2, p3 = p2 a3; inv runs 1/p3, 1/p2, 1/p1
+            const T p1 = u_fit<1, 3>(u_mul(get(0), get(1)));
+            const T p2 = u_fit<1, 3>(u_mul(p1, get(2)));
+            Fe<L> c;
+            u_to_canonical<CU>(c, u_mul(p2, get(3)));
+            fe_inv_gcd<CS>(c, c);
+            T inv = u_as<1, 3>(u_to_mont<CU>(c));
+            {
+              const T a3 = get(3);
+              put(3, u_fit<1, 3>(u_mul(inv, p2)));
+              inv = u_fit<1, 3>(u_mul(inv, a3));
+            }
+            {
+              const T a2 = get(2);
+              put(2, u_fit<1, 3>(u_mul(inv, p1)));
+              inv = u_fit<1, 3>(u_mul(inv, a2));
+            }
+            const T a0 = get(0), a1 = get(1);
+            put(0, u_fit<1, 3>(u_mul(inv, a1)));
+            put(1, u_fit<1, 3>(u_mul(inv, a0)));
+          }
+          __syncthreads();
+#pragma unroll
+          for (int i = 0; i < N; ++i) lam.v[i] = zsh[i][tid];
+          __syncthreads();  // the next iteration's values must not overtake these reads
+        } else {
+          // 1 / zeta (zeta = 0 only for degenerate units, which are redone anyway: the inverse of 0 is 0)
+          Fe<L> c;
+          u_to_canonical<CU>(c, zacc);
+          fe_inv_gcd<CS>(c, c);
+          lam = u_as<1, 3>(u_to_mont<CU>(c));
+        }
         const T l2 = u_fit<1, 3>(u_sqr(lam));
         const T l3 = u_fit<1, 3>(u_mul(l2, lam));
         const T xt = u_fit<1, 3>(u_mul(tx, l2)), yt = u_fit<1, 3>(u_mul(ty, l3));
@@ -738,14 +811,16 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         }
       }
     } else {
-      constexpr int LAST_SUB = GLV ? WB + 1 : WB;  // sub 0..WB-1: doublings, WB: addition (WB+1: second half's addition)
+      // sub 0..nd-1: doublings, nd: addition (nd+1: second half's addition); nd = WB but for the bottom window of the
+      // top-aligned form (win = -1), which has S
+      constexpr int WIN_END = S != 0 ? -1 : 0;
       int win, sub;
       {
         // the top window's (first) addition has nothing to add to: the accumulator starts as that signed
         // entry -- affine, so Z = 1 -- or at infinity for digit 0
         uint32_t d;
         bool neg;
-        booth(NWIN - 1, false, d, neg);
+        booth(NWIN_MAIN - 1, false, d, neg);
         T tx, ty;
         u2_load<CU>(tx, ty, row(d ? d : 1));
         U<CU, 2, 4> sy;
@@ -755,17 +830,18 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         q.z = u_as<UJac<CU>::ZK, UJac<CU>::ZV>(one);
         if (d == 0) u_set_zero(q.z);
         if constexpr (GLV) {
-          win = NWIN - 1;
+          win = NWIN_MAIN - 1;
           sub = WB + 1;  // the second half's addition of the top window comes next
         } else {
-          win = NWIN - 2;
+          win = NWIN_MAIN - 2;
           sub = 0;
         }
       }
       bool fix_pending = false, fix_lane = false;
-      while (win >= 0) {
+      while (win >= WIN_END) {
+        const int nd = (S != 0 && win < 0) ? S : WB;
         bool step_done;
-        if (fix_pending || sub < WB) {
+        if (fix_pending || sub < nd) {
           UJac<CU> t;
           if constexpr (UBS<CU>::DENSE) {
             // P-256: the merged doubling, and the equal-points fix-up in a wave-uniform branch of its own.  Its
@@ -831,7 +907,7 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
           step_done = !fix_pending;
         }
         if (step_done) {
-          if (sub < LAST_SUB) {
+          if (sub < nd + (GLV ? 1 : 0)) {
             ++sub;
           } else {
             sub = 0;

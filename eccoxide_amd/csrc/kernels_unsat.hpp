@@ -313,6 +313,27 @@ ECCX_DEV void booth_digit(const uint8_t* __restrict__ k, int w, uint32_t& d, boo
   d = (m >> 1) + (m & 1u);
   neg = (s & 1u) != 0;
 }
+// The same recoding with the windows aligned to the TOP of the 8 SB + 1 Booth positions: S = (8 SB + 1) mod W > 0
+// scalar bits stay below the main windows.  Main window w >= 0 covers bits W w + S .. W w + S + W - 1 (borrow bit
+// W w + S - 1); w = -1 is the bottom digit from bits S - 1 .. 0 (no borrow below bit 0), |d| <= 2^(S-1):
+//   k = sum_w d_w 2^(W w + S) + d_bottom.
+// The top main window ends at bit 8 SB, which is zero, so its digit is never negative.  Model:
+// tests/test_booth_aligned_cpu.py.
+template <int W, int SB, int S>
+ECCX_DEV void booth_digit_aligned(const uint8_t* __restrict__ k, int w, uint32_t& d, bool& neg) {
+  static_assert(W >= 2 && W <= 8 && S >= 1 && S < W, "a window and its borrow bit must fit two bytes at any bit offset");
+  const bool bottom = w < 0;
+  const int pos = bottom ? 7 : W * w + S - 1 + 8;  // as in booth_digit; the bottom digit's borrow is the (zero) bit -1
+  const int width = bottom ? S : W;
+  const int bi = pos >> 3;
+  const uint32_t b0 = (bi >= 1 && bi <= SB) ? k[SB - bi] : 0u;
+  const uint32_t b1 = (bi + 1 <= SB) ? k[SB - bi - 1] : 0u;
+  const uint32_t wv = ((b0 | (b1 << 8)) >> (pos & 7)) & ((2u << width) - 1u);
+  const uint32_t s = ~((wv >> width) - 1u);  // all ones for a negative digit
+  const uint32_t m = (((2u << width) - wv - 1u) & s) | (wv & ~s);
+  d = (m >> 1) + (m & 1u);
+  neg = (s & 1u) != 0;
+}
 
 template <class CU, bool FROM_INFINITY = false>
 ECCX_DEV void ucomb_accumulate(UJac<CU>& q, const uint8_t* __restrict__ k, const uint32_t* __restrict__ table);
