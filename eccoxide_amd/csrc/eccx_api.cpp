@@ -848,6 +848,7 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     rc = ensure_slab<EdSignSlab>(ctx, B_EDSIGN, ops, max_n, nullptr);
   if (!rc && (what & ECCX_PREP_ECDSA_SIGN) && ops->ecdsa_sign_finish)
     rc = ensure_slab<EcdsaSignSlab>(ctx, B_ECSIGN, ops, max_n, nullptr);
+  // eccx_hash_to_g1 works in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C asks for nothing more)
   return rc;
 }
 
@@ -1333,6 +1334,46 @@ int eccx_ed25519_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64
       },
       [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
   return wipe_io(ctx, rc, bufs[0], nullptr, n);
+}
+
+int eccx_hash_to_g1_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        void* d_out, void* d_flags, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_H2C_NU) return arg_err(ctx, "eccx_hash_to_g1: opts must be 0 or ECCX_H2C_NU (the messages are public)");
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_msgs && d_offsets && d_out && d_flags && (dst || dst_len == 0))) return rc;
+  const CurveOps* ops = ops_of(ECCX_BLS12_381_G1);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int count = (opts & ECCX_H2C_NU) ? 1 : 2;
+  eccx::H2cTag tag;
+  eccx::h2c_host::pack_tag(tag, dst, dst_len, 64u * (uint32_t)count);
+  if (int rc = ensure_rows(ctx, ops, n)) return rc;
+  uint8_t* flags = static_cast<uint8_t*>(d_flags);
+  // hash_to_field into the rows; map, add, clear the cofactor in place; normalise
+  HIP_TRY(ctx, ops->h2c_hash_to_field(grid(ctx, n, 8), s, n, static_cast<const uint8_t*>(d_msgs), static_cast<const uint64_t*>(d_offsets),
+                                      tag, count, ctx->rows(), flags));
+  HIP_TRY(ctx, ops->h2c_map_finish(ops->h2c_map_grid(ctx->cus, n), s, n, count, ctx->rows()));
+  HIP_TRY(ctx, ops->to_affine_var(norm_grid(ctx, n), s, n, ctx->rows(), static_cast<uint8_t*>(d_out), flags));
+  return ECCX_OK;
+}
+
+int eccx_hash_to_g1(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    uint8_t* out, uint8_t* flags, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_H2C_NU) return arg_err(ctx, "eccx_hash_to_g1: opts must be 0 or ECCX_H2C_NU (the messages are public)");
+  if (n == 0) return ECCX_OK;
+  if (!offsets || !out || !flags || (!dst && dst_len != 0)) return arg_err(ctx, "null buffer");
+  EdMsgs m{msgs, offsets};
+  if (int rc = m.check(ctx, n, "eccx_hash_to_g1: the offsets decrease")) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = m.grow_slots(ctx, n)) return rc;
+  HostBuf bufs[] = {out_buf(IO_O, out, 96), out_buf(IO_F, flags, 1)};
+  return host_pipeline(
+      ctx, n, bufs, /*chunked=*/true,
+      [&](size_t lo, size_t cnt, uint8_t* const* d) {
+        return eccx_hash_to_g1_dev(ctx, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d[1], opts, ctx->stream);
+      },
+      [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
 }
 
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,

@@ -11,6 +11,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "h2c_tag.hpp"
+
 namespace eccx {
 
 struct CurveInfo {
@@ -158,6 +160,14 @@ struct CurveOps {
                                   const uint8_t* nonces, const uint8_t* xs, const uint8_t* lflags, uint8_t* sigs, uint8_t* status);
   hipError_t (*ecdsa_pubkey_finish)(int grid, hipStream_t s, size_t n, const uint8_t* secrets, const uint8_t* lflags, uint8_t* out,
                                     int width, uint8_t* status);
+  // Hashing to the curve (kernels_h2c.hpp; bls12_381_g1 only, else null).  h2c_hash_to_field hashes the messages (as
+  // ed_verify_prepare takes them) under the call's tag to `count` field elements per unit (1: encode_to_curve, 2:
+  // hash_to_curve), parked in the unit's result row, and writes flags 0, or 2 for a lane whose offsets decrease.
+  // h2c_map_finish maps them to the curve, adds, clears the cofactor and leaves (X, Y, Z) in the row for to_affine_var.
+  hipError_t (*h2c_hash_to_field)(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const H2cTag& tag,
+                                  int count, uint32_t* rows, uint8_t* flags);
+  hipError_t (*h2c_map_finish)(int grid, hipStream_t s, size_t n, int count, uint32_t* rows);
+  int (*h2c_map_grid)(int cus, size_t n);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above

@@ -27,11 +27,13 @@ ASSUME_SUBGROUP = 1 << 9
 CT_GATHER = 1 << 10
 OUT_X_ONLY = 1 << 11
 PUBKEY_SEC1 = 1 << 12
+H2C_NU = 1 << 13
 PREP_VAR, PREP_BASE, PREP_BASE_LDS, PREP_MIRROR, PREP_CT, PREP_CT_GATHER, PREP_HOST = 1, 2, 4, 8, 16, 32, 64
 PREP_ECDSA = 128
 PREP_ED25519 = 256
 PREP_ED25519_SIGN = 512
 PREP_ECDSA_SIGN = 1024
+PREP_H2C = 2048
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
 SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
@@ -145,17 +147,19 @@ class Engine:
                                            | (PREP_CT if ct else 0) | (PREP_CT_GATHER if ct_gather else 0)))
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
-                ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False):
+                ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
+                h2c: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
-        row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key."""
+        row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key; h2c: the row buffer
+        hash_to_g1 works in (curve "bls12_381_g1")."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
                                            | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)
                                            | (PREP_ED25519_SIGN if ed25519_sign else 0)
-                                           | (PREP_ECDSA_SIGN if ecdsa_sign else 0)))
+                                           | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -429,6 +433,58 @@ class Engine:
         self._check(self._lib.eccx_ed25519_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), sigs.data_ptr(),
                                                       pubkeys.data_ptr(), verdicts.data_ptr(), 0, stream))
         return verdicts
+
+    def hash_to_g1(self, messages, dst: bytes, *, nonuniform: bool = False):
+        """Hash a batch of messages to BLS12-381 G1 (eccx_hash_to_g1; RFC 9380, g1::Point::hash_to_curve): messages is a
+        list of n byte strings, dst the domain separation tag of the call (any length).  nonuniform selects
+        encode_to_curve (the ..._NU_ suite).  Returns (points n x 96 affine x || y, flags n)."""
+        import numpy as np
+
+        n = len(messages)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(m) for m in messages], out=offsets[1:])
+        msgs = b"".join(bytes(m) for m in messages)
+        dst = bytes(dst)
+        out = ctypes.create_string_buffer(max(1, 96 * n))
+        flags = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_hash_to_g1(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, dst if dst else None,
+                                              len(dst), out, flags, H2C_NU if nonuniform else 0))
+        return out.raw[:96 * n], flags.raw[:n]
+
+    def hash_to_g1_t(self, msgs, offsets, dst: bytes, out=None, flags=None, *, nonuniform: bool = False,
+                     stream: Optional[int] = None, check_bounds: bool = True):
+        """Device-tensor form of hash_to_g1 (eccx_hash_to_g1_dev): msgs and offsets as in ed25519_verify_t, dst host bytes.
+        Enqueued on `stream` (default: torch's current stream); returns (points n x 96, flags n) tensors -- what
+        scalarmul_var_t and point_compress_t take.  A lane whose offsets decrease is flagged FLAG_REJECTED.  check_bounds
+        as in ed25519_verify_t."""
+        import torch
+
+        n = offsets.numel() - 1
+        if offsets.dtype not in (torch.int64, torch.uint64) or n < 0 or not offsets.is_contiguous():
+            raise ValueError("offsets must be a contiguous int64 tensor of n + 1 entries")
+        if not offsets.is_cuda or not msgs.is_cuda or msgs.dtype != torch.uint8 or not msgs.is_contiguous():
+            raise ValueError("msgs (contiguous uint8) and offsets must be CUDA tensors")
+        if out is None:
+            out = torch.empty((n, 96), dtype=torch.uint8, device=offsets.device)
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.uint8, device=offsets.device)
+        self._tensors(n, ("out", out, 96), ("flags", flags, 1))
+        for name, t in (("msgs", msgs), ("offsets", offsets)):
+            if t.device.index != self.device:
+                raise ValueError(f"{name}: tensor lives on cuda:{t.device.index}, this engine is bound to cuda:{self.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(offsets.device).cuda_stream
+        if check_bounds and n:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=offsets.device)):
+                lo, hi, first = (int(v) for v in torch.stack([offsets.min(), offsets.max(), offsets[0]]).cpu())
+            if lo < 0 or hi - first > msgs.numel():
+                raise ValueError(f"offsets span {hi - first} bytes from offsets[0] (min {lo}); msgs holds {msgs.numel()}")
+        if msgs.numel() == 0:  # every message empty: any valid address
+            msgs = torch.zeros((1,), dtype=torch.uint8, device=offsets.device)
+        dst = bytes(dst)
+        self._check(self._lib.eccx_hash_to_g1_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None, len(dst),
+                                                  out.data_ptr(), flags.data_ptr(), H2C_NU if nonuniform else 0, stream))
+        return out, flags
 
     def ed25519_public_key(self, seeds: bytes, *, ct_gather: bool = False) -> bytes:
         """Ed25519 public keys of a batch of seeds (eccx_ed25519_public_key; SecretKey::public_key): seeds n x 32, the

@@ -24,6 +24,9 @@
  *   eccx_ed25519_verify[_dev]    Ed25519 verification            src/protocol/ed25519.rs:119-146
  *   eccx_ed25519_public_key[_dev]  SecretKey::public_key        src/protocol/ed25519.rs:62-80, 175-190
  *   eccx_ed25519_sign[_dev]      SecretKey::sign / Keypair::sign   src/protocol/ed25519.rs:91-117, 192-247
+ *   eccx_hash_to_g1[_dev]        g1::Point::hash_to_curve / encode_to_curve   src/curve/bls12_381/g1.rs:181-201
+ *                              -> expand_message_xmd, hash_to_field, map_to_curve_g1   src/curve/bls12_381/hash_to_curve.rs:77-134,
+ *                              :454-520; clear_cofactor g1.rs:131-134
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
@@ -81,6 +84,9 @@
  * against 2.25-2.29 for the p256r1 comb) -- the frequency side channel every DVFS processor has, the reference's
  * CPUs included; two batches of independent random scalars are indistinguishable at the precision of that
  * measurement.  GPU schedulers and caches are not modelled beyond these measurements.
+ * eccx_hash_to_g1 treats its messages as PUBLIC and makes no secret-data promise.  The reference's map is branch-free
+ * (hash_to_curve.rs:325-350); ours resolves the map's own cases by selects as well, but a lane's SHA-256 block count
+ * follows its message length, and the additions behind the map take wave-uniform branches on Q0 = +-Q1.
  *
  * MEMORY AND BLOCKING.  A context is bound to one GPU and owns
  *   - the window-table slab of the variable-base ladders: resident lanes x 17 rows (P-256:
@@ -174,6 +180,8 @@ enum {
   ECCX_OUT_X_ONLY = 1u << 11,      /* eccx_double_scalarmul: write the x-coordinate alone, FB bytes per unit (`out` is then
                                       n x FB): Point::to_affine_x_ct (src/curve/projective.rs:690), which is all ECDSA
                                       verification reads (src/protocol/ecdsa.rs:383).  Weierstrass curves. */
+  ECCX_H2C_NU = 1u << 13,          /* eccx_hash_to_g1: the nonuniform suite BLS12381G1_XMD:SHA-256_SSWU_NU_ (encode_to_curve:
+                                      one field element, one map) instead of ..._RO_ (hash_to_curve) */
   ECCX_ASSUME_SUBGROUP = 1u << 9   /* eccx_scalarmul_var, bls12_381_g1: the caller guarantees every base point
                                       is in the prime-order subgroup G1 (e.g. it was decoded under
                                       ECCX_CHECK_SUBGROUP, or is a multiple of the generator).  The
@@ -202,6 +210,9 @@ enum {
                                    comb's scalars, its output and flags) and the fixed-base row buffer, for 2 * max_n lanes */
   ECCX_PREP_ECDSA_SIGN = 1u << 10, /* eccx_reserve: the working slab of eccx_ecdsa_sign / eccx_ecdsa_public_key (the comb's
                                    output and flags) and the fixed-base row buffer */
+  ECCX_PREP_H2C = 1u << 11,     /* eccx_reserve (bls12_381_g1): the result-row buffer eccx_hash_to_g1 works in (it has no other
+                                   slab); with ECCX_PREP_HOST the copies of the host form's points and flags -- its message
+                                   slot grows on demand, as Ed25519's does */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -416,6 +427,32 @@ int eccx_ed25519_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64
                       const uint8_t* pubkeys, uint8_t* sigs, uint32_t opts);
 int eccx_ed25519_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const void* d_seeds,
                           const void* d_pubkeys, void* d_sigs, uint32_t opts, void* stream);
+
+/* Hashing to BLS12-381 G1, batched (RFC 9380; g1::Point::hash_to_curve / encode_to_curve, src/curve/bls12_381/g1.rs:
+ * 181-201): the first step of a BLS signature, H(m).
+ *   msgs, offsets : as in eccx_ed25519_verify (n + 1 uint64, relative to offsets[0]; msgs may be NULL in the host form when
+ *                   every message is empty)
+ *   dst, dst_len  : the domain separation tag of the call, HOST memory in both forms (it is public and short).  Any
+ *                   length: dst_len == 0 is legal (dst may then be NULL), and a tag over 255 bytes is replaced on the
+ *                   host by SHA-256("H2C-OVERSIZE-DST-" || dst) (RFC 9380 5.3.3, hash_to_curve.rs:88-96)
+ *   out           : n x 96, affine x || y big-endian -- the record eccx_scalarmul_var[_dev] and eccx_point_compress[_dev]
+ *                   take, so hash -> sk * H(m) (ECCX_CT_SCAN | ECCX_ASSUME_SUBGROUP) -> compress stays on the GPU
+ *   flags         : n bytes.  0: a point of G1.  ECCX_FLAG_INFINITY with zero bytes: the identity, which only constructed
+ *                   field elements reach.  ECCX_FLAG_REJECTED with zero bytes: a lane of the _dev form whose offsets
+ *                   decrease (against the next one or against offsets[0]); it reads nothing, the other lanes stand.
+ *   opts          : 0 selects the suite BLS12381G1_XMD:SHA-256_SSWU_RO_ (hash_to_curve: two field elements, two maps, one
+ *                   addition, cofactor cleared), ECCX_H2C_NU selects ..._NU_ (encode_to_curve: one element, one map).
+ *                   Anything else, ECCX_CT_SCAN included, is ECCX_ERR_ARG: the messages are public (SIDE CHANNELS above).
+ * On the GPU, all of it: expand_message_xmd with SHA-256, the reduction of 64 bytes mod p, Simplified SWU onto the
+ * 11-isogenous curve, the isogeny, Q0 + Q1 and the cofactor chain P + [|x|]P, then the batched normalisation.
+ * n == 0 returns ECCX_OK whatever the pointers.  The host form checks that the offsets never decrease before it touches
+ * the device (ECCX_ERR_ARG).  The _dev form enqueues on `stream` without synchronising and works in the context's
+ * result-row buffer (grow-only; eccx_reserve with ECCX_PREP_H2C sizes it): after that a call with n <= max_n neither
+ * allocates, frees nor synchronises. */
+int eccx_hash_to_g1(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    uint8_t* out, uint8_t* flags, uint32_t opts);
+int eccx_hash_to_g1_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        void* d_out, void* d_flags, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

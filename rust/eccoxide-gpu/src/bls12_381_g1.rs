@@ -1,6 +1,6 @@
 //! BLS12-381 G1 (`src/curve/bls12_381/g1.rs`, a = 0 Weierstrass over Fp): batch scalar
 //! multiplication, the zcash encodings (`src/curve/bls12_381/serialize.rs:253-383`) and the
-//! subgroup membership test (`g1.rs:90-109`).
+//! subgroup membership test (`g1.rs:90-109`), and hashing to the group (`g1.rs:181-201`, RFC 9380).
 use eccoxide::curve::bls12_381::g1::PointAffine;
 use eccoxide::curve::bls12_381::{Fp, Scalar};
 
@@ -124,4 +124,35 @@ pub fn is_in_subgroup_batch(ctx: &GpuContext, points: &[PointAffine]) -> Result<
                                    ffi::ECCX_UNCOMPRESSED | ffi::ECCX_CHECK_SUBGROUP)
     })?;
     Ok(flags.iter().map(|&f| f == ffi::ECCX_FLAG_FINITE).collect())
+}
+
+fn hash_batch(ctx: &GpuContext, messages: &[&[u8]], dst: &[u8], opts: u32) -> Result<Vec<Unit<PointAffine>>, GpuError> {
+    let n = messages.len();
+    let mut offsets = Vec::with_capacity(n + 1);
+    let mut msgs = Vec::new();
+    offsets.push(0u64);
+    for m in messages {
+        msgs.extend_from_slice(m);
+        offsets.push(msgs.len() as u64);
+    }
+    let (mut out, mut flags) = (vec![0u8; n * 2 * FB], vec![0u8; n]);
+    ctx.check(unsafe {
+        ffi::eccx_hash_to_g1(ctx.raw(), n, if msgs.is_empty() { core::ptr::null() } else { msgs.as_ptr() }, offsets.as_ptr(),
+                             if dst.is_empty() { core::ptr::null() } else { dst.as_ptr() }, dst.len(), out.as_mut_ptr(),
+                             flags.as_mut_ptr(), opts)
+    })?;
+    Ok(parse_points(&out, &flags))
+}
+
+/// `Point::hash_to_curve(messages[i], dst)` (g1.rs:181-190; RFC 9380 suite `BLS12381G1_XMD:SHA-256_SSWU_RO_`) over a
+/// batch, in one call into the library (`eccx_hash_to_g1`): `expand_message_xmd`, the reduction mod p, both maps, the
+/// addition and the cofactor clearing all run on the GPU.  The messages are treated as public.  The identity, which only
+/// constructed field elements reach, comes back as `Unit::Infinity`.
+pub fn hash_to_curve_batch(ctx: &GpuContext, messages: &[&[u8]], dst: &[u8]) -> Result<Vec<Unit<PointAffine>>, GpuError> {
+    hash_batch(ctx, messages, dst, 0)
+}
+
+/// `Point::encode_to_curve(messages[i], dst)` (g1.rs:192-201; the nonuniform suite `..._NU_`) over a batch.
+pub fn encode_to_curve_batch(ctx: &GpuContext, messages: &[&[u8]], dst: &[u8]) -> Result<Vec<Unit<PointAffine>>, GpuError> {
+    hash_batch(ctx, messages, dst, ffi::ECCX_H2C_NU)
 }

@@ -4,10 +4,15 @@
 
 Self-contained (standard SEC 2 / BLS12-381 / RFC 8032 constants, plain big-int
 math); does not import oracle/ or read /root/reference.  tests/ cross-check the
-generated values against tests/golden/params.json.
+generated values against tests/golden/params.json.  The one input is tests/golden/bls_h2c.json:
+RFC 9380's constants for hashing to BLS12-381 G1 (section 8.8.1, appendix E.2), checked here
+for what makes them the right constants before they are emitted.
 
     python tools/gen_curve_consts.py > eccoxide_amd/csrc/curve_consts.inc
 """
+import json
+import os
+import random
 import sys
 
 CURVES = [
@@ -321,6 +326,69 @@ def emit_sat(out, name, p, b, gx, gy, fb, sb, a0):
     out.append("")
 
 
+def arr2(name, rows):
+    body = ",\n".join("      {%s}" % ", ".join("0x%08xu" % v for v in r) for r in rows)
+    return "  static constexpr uint32_t %s[%d][%d] = {\n%s};" % (name, len(rows), len(rows[0]), body)
+
+
+def emit_bls_h2c(out):
+    """BLS12_381_H2C: the constants of hash_to_curve / encode_to_curve for G1 (kernels_h2c.hpp) in the working form of
+    BLS12_381U (14 x 28-bit Montgomery digits): the isogenous curve E': y^2 = x^3 + A'x + B', Z = 11, sqrt(-Z), the
+    11-isogeny's four polynomials (ascending; the denominators monic, leading 1 not stored), 2^256 R^2 for the
+    512-bit reduction and the exponent (p - 3) / 4 of sqrt_ratio_3mod4."""
+    _, p, b, _, _, _, _, _ = CURVES[3]
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "bls_h2c.json")
+    with open(path) as f:
+        c = json.load(f)["constants"]
+    z = c["z"]
+    ia, ib, c2 = int(c["iso_a"], 16), int(c["iso_b"], 16), int(c["sqrt_minus_z"], 16)
+    polys = {k: [int(h, 16) for h in c[k]] for k in ("x_num", "x_den", "y_num", "y_den")}
+    # what makes them the right constants
+    assert p % 4 == 3 and all(0 <= v < p for v in [ia, ib, c2] + sum(polys.values(), []))
+    assert c2 * c2 % p == (-z) % p, "c2 is not a square root of -Z"
+    assert pow(z, (p - 1) // 2, p) == p - 1, "Z is a square"
+    assert ia * ib % p != 0
+    assert [len(polys[k]) for k in ("x_num", "x_den", "y_num", "y_den")] == [12, 10, 16, 15], "degrees of the 11-isogeny"
+    assert polys["x_num"][-1] != 0 and polys["y_num"][-1] != 0
+
+    def ev(co, x, monic):
+        acc = sum(v * pow(x, i, p) for i, v in enumerate(co))
+        return (acc + (pow(x, len(co), p) if monic else 0)) % p
+
+    rng = random.Random(9380)
+    seen = 0
+    while seen < 16:  # random points of E' land on y^2 = x^3 + 4
+        x = rng.randrange(p)
+        g = (x * x * x + ia * x + ib) % p
+        y = pow(g, (p + 1) // 4, p)
+        if y * y % p != g:
+            continue
+        xd, yd = ev(polys["x_den"], x, True), ev(polys["y_den"], x, True)
+        if xd == 0 or yd == 0:
+            continue
+        X = ev(polys["x_num"], x, False) * pow(xd, -1, p) % p
+        Y = y * ev(polys["y_num"], x, False) * pow(yd, -1, p) % p
+        assert (Y * Y - X * X * X - b) % p == 0, "the isogeny misses the curve"
+        seen += 1
+    bits, n = 28, 14
+    R = 1 << (bits * n)
+    mont = lambda v: digits(v * R % p, bits, n)
+    out.append("")
+    out.append("struct BLS12_381_H2C {  // RFC 9380 8.8.1 / E.2: hashing to G1, working form of BLS12_381U")
+    out.append(arr("A", mont(ia)))
+    out.append(arr("B", mont(ib)))
+    out.append(arr("Z", mont(z)))
+    out.append(arr("SQRT_MZ", mont(c2)) + "  // sqrt(-Z)")
+    out.append(arr("R2_256", digits((1 << 256) * R * R % p, bits, n)) + "  // 2^256 R^2: a * R2_256 / R = a 2^256 R")
+    for k in ("x_num", "x_den", "y_num", "y_den"):
+        out.append(arr2(k.upper().replace("_", ""), [mont(v) for v in polys[k]]))
+    e = (p - 3) // 4
+    nw = (e.bit_length() + 31) // 32
+    out.append("  static constexpr int ROOT_BITS = %d;  // of (p - 3) / 4" % e.bit_length())
+    out.append("  static constexpr uint32_t ROOT_EXP[%d] = {%s};" % (nw, ", ".join("0x%08xu" % ((e >> (32 * i)) & 0xFFFFFFFF) for i in range(nw))))
+    out.append("};")
+
+
 def main():
     out = ["// @generated by tools/gen_curve_consts.py -- do not edit.",
            "// Montgomery constants, 32-bit little-endian limbs, R = 2^(32*L).", ""]
@@ -401,6 +469,7 @@ def main():
     out.append("  static constexpr int NBITS = %d;  // bit length of l" % ell.bit_length())
     emit_field(out, ell, 8)
     out.append("};")
+    emit_bls_h2c(out)
     sys.stdout.write("\n".join(out) + "\n")
 
 

@@ -91,7 +91,7 @@ def main():
         mad_cyc = c["v_mad_u64_u32"] * COST["v_mad_u64_u32"] + c["v_mad_i64_i32"] * COST["v_mad_i64_i32"]
         tot = sum(c.values())
         print(f"\n{name}: {tot} instructions, {sum(valu.values())} VALU, {mads} multiplies "
-              f"({100.0 * mads / max(1, sum(valu.values())):.1f} % of VALU instructions, {100.0 * mad_cyc / cyc:.1f} % of VALU issue cycles)")
+              f"({100.0 * mads / max(1, sum(valu.values())):.1f} % of VALU instructions, {100.0 * mad_cyc / max(cyc, 1e-9):.1f} % of VALU issue cycles)")
         for k, v in c.most_common():
             print(f"    {v:6d}  {k}")
 
