@@ -22,7 +22,7 @@ namespace {
 
 using eccx::CurveOps;
 
-constexpr int NCURVES = 6;
+constexpr int NCURVES = 8;  // curve ids 0 .. 7 (6 is unassigned)
 // internal kernel option bits (kernels.hpp)
 constexpr uint32_t K_BASE_IS_GENERATOR = 1u << 0;
 constexpr uint32_t K_OUT_TABLE = 1u << 1;
@@ -40,6 +40,7 @@ const CurveOps* ops_of(int curve) {
     case ECCX_BLS12_381_G1: return &eccx::ops_BLS12_381();
     case ECCX_ED25519: return &eccx::ops_ED25519();
     case ECCX_P256K1: return &eccx::ops_P256K1();
+    case ECCX_BLS12_381_G2: return &eccx::ops_BLS12_381_G2();
     default: return nullptr;
   }
 }
@@ -262,13 +263,15 @@ int launch_var(eccx_ctx* ctx, const CurveOps* ops, size_t n, const uint8_t* d_sc
     // ct_prime: the bases are vouched to have prime order (ECCX_ASSUME_SUBGROUP on a curve with a cofactor)
     const bool ed = ops->info.edwards != 0;
     const bool prime = ct_prime && ops->var_ct_prime;
-    const Need ladder = need_var_ct(ctx, ops, n, prime), fixup = ed ? Need{0, 0} : need_var_fixup(ctx, ops, n);
+    // (no fix-up where the ladder itself is complete and marks nothing: edwards25519, bls12_381_g2)
+    const bool fix = !ed && ops->var;
+    const Need ladder = need_var_ct(ctx, ops, n, prime), fixup = fix ? need_var_fixup(ctx, ops, n) : Need{0, 0};
     const int rc = ensure_work(ctx, ops, n, {ladder, fixup});
     if (rc) return rc;
     HIP_TRY(ctx, (prime ? ops->var_ct_prime : ops->var_ct)(ladder.grid, s, n, d_scalars, d_points, ctx->rows(), d_flags,
                                                            ctx->scratch(), kopts & ~K_CT_SCAN));
     HIP_TRY(ctx, ops->to_affine_var(norm_grid(ctx, n), s, n, ctx->rows(), d_out, d_flags));
-    if (!ed)
+    if (fix)
       HIP_TRY(ctx, ops->var(fixup.grid, s, n, d_scalars, d_points, d_out, d_flags, nullptr, ctx->scratch(),
                             (kopts & K_VALIDATE) | K_CT_SCAN | K_ONLY_MARKED));
     return ECCX_OK;
@@ -391,7 +394,11 @@ int no_fix_up(uint8_t*, uint8_t*) { return ECCX_OK; }
 
 // the reference-layout table, written by the mirror kernel itself, and the wide-window table of the unsaturated
 // fixed-base kernel: entry (w, d) = d * 2^(W*w) * G
+int ensure_comb_ct(eccx_ctx* ctx, int curve, const CurveOps* ops, bool gather);
 int ensure_comb(eccx_ctx* ctx, int curve, const CurveOps* ops) {
+  // a curve without the reference-mirroring kernels (bls12_381_g2) keeps ONE fixed-base table, in the reference's 4-bit
+  // layout, which both of its combs read: the one ensure_comb_ct builds
+  if (!ops->var) return ensure_comb_ct(ctx, curve, ops, false);
   std::lock_guard<std::mutex> g(ctx->comb_mu);
   if (ctx->table[T_COMB][curve]) return ECCX_OK;
   HIP_TRY(ctx, hipDeviceSynchronize());
@@ -469,6 +476,19 @@ int launch_comb_ct(eccx_ctx* ctx, int curve, const CurveOps* ops, size_t n, cons
   HIP_TRY(ctx, (gather ? ops->base_ctg : ops->base_ct)(grid(ctx, n, 16), s, n, d_scalars, ctx->table[gather ? T_CTG : T_CT][curve],
                                                        ctx->rows(), d_flags));
   HIP_TRY(ctx, (x_only ? ops->to_affine_x : ops->to_affine_var)(norm_grid(ctx, n), s, n, ctx->rows(), d_out, d_flags));
+  return ECCX_OK;
+}
+
+// A curve without the reference-mirroring kernels (bls12_381_g2: var, base and point_add are null) serves neither the
+// un-normalised X:Y:Z nor the options that select those kernels or the tables only they read; `also`: further options
+// the entry point cannot serve on such a curve
+int mirror_only_err(eccx_ctx* ctx, const CurveOps* ops, const void* proj, uint32_t opts, uint32_t also) {
+  if (ops->var) return ECCX_OK;
+  if (proj) return arg_err(ctx, "proj: this curve has no reference-mirroring kernels (no X:Y:Z output on bls12_381_g2)");
+  if (opts & ECCX_MIRROR_REFERENCE)
+    return arg_err(ctx, "ECCX_MIRROR_REFERENCE: this curve has no reference-mirroring kernels (bls12_381_g2)");
+  if (opts & also)
+    return arg_err(ctx, "ECCX_TABLE_IN_LDS / ECCX_TABLE_IN_L2 / ECCX_CT_GATHER: bls12_381_g2 has one fixed-base table, read by index or by scan");
   return ECCX_OK;
 }
 
@@ -866,6 +886,7 @@ int eccx_scalarmul_var_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_sca
                            void* d_out, void* d_flags, void* d_proj, uint32_t opts, void* stream) {
   const CurveOps* ops;
   if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = mirror_only_err(ctx, ops, d_proj, opts, 0)) return rc;
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_scalars && d_points && d_out && d_flags)) return rc;
   // ECCX_CT_SCAN: the reference-mirroring ladder (complete formulas, no data-dependent branch) with
@@ -890,11 +911,23 @@ int eccx_scalarmul_base_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_sc
                             void* d_proj, uint32_t opts, void* stream) {
   const CurveOps* ops;
   if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = mirror_only_err(ctx, ops, d_proj, opts, ECCX_TABLE_IN_LDS | ECCX_TABLE_IN_L2 | ECCX_CT_GATHER)) return rc;
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_scalars && d_out && d_flags)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
   const uint8_t* scalars = static_cast<const uint8_t*>(d_scalars);
   uint8_t *out = static_cast<uint8_t*>(d_out), *flags = static_cast<uint8_t*>(d_flags), *proj = static_cast<uint8_t*>(d_proj);
+  if (!ops->base) {
+    // bls12_381_g2: one table in the reference's 4-bit layout under both combs -- read by the digit, or (ECCX_CT_SCAN)
+    // every entry of the window read by every lane
+    int rc = ensure_comb_ct(ctx, curve, ops, false);
+    if (!rc) rc = ensure_rows(ctx, ops, n);
+    if (rc) return rc;
+    HIP_TRY(ctx, ((opts & ECCX_CT_SCAN) ? ops->base_ct : ops->base_unsat)(grid(ctx, n, 16), s, n, scalars, ctx->table[T_CT][curve],
+                                                                        ctx->rows(), flags));
+    HIP_TRY(ctx, ops->to_affine_var(norm_grid(ctx, n), s, n, ctx->rows(), out, flags));
+    return ECCX_OK;
+  }
   if ((opts & ECCX_CT_SCAN) && !(opts & (ECCX_MIRROR_REFERENCE | ECCX_TABLE_IN_L2)) && !proj && ops->base_ct) {
     // secret scalars: signed windows, every entry of a window read by every lane (kernels_ct.hpp)
     if (opts & ECCX_TABLE_IN_LDS) {
@@ -958,6 +991,7 @@ int eccx_point_add_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_a, cons
   if (int rc = enter(ctx, curve, &ops)) return rc;
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_a && d_b && d_out && d_flags)) return rc;
+  if ((opts & ECCX_MIRROR_REFERENCE) && !ops->point_add) return mirror_only_err(ctx, ops, nullptr, opts, 0);
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint8_t* flags = static_cast<uint8_t*>(d_flags);
   int rc = ensure_rows(ctx, ops, n);
@@ -1006,7 +1040,7 @@ int eccx_point_decompress_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_
   const uint8_t* enc = static_cast<const uint8_t*>(d_enc);
   uint8_t *out = static_cast<uint8_t*>(d_out), *flags = static_cast<uint8_t*>(d_flags);
   if (opts & ECCX_UNCOMPRESSED) {
-    if (!ops->decompress_raw) return arg_err(ctx, "ECCX_UNCOMPRESSED: the flavour exists for bls12_381_g1 only");
+    if (!ops->decompress_raw) return arg_err(ctx, "ECCX_UNCOMPRESSED: the flavour exists for bls12_381_g1 and bls12_381_g2 only");
     HIP_TRY(ctx, ops->decompress_raw(grid(ctx, n, 8), s, n, enc, out, flags));
   } else {
     HIP_TRY(ctx, ops->decompress(grid(ctx, n, 8), s, n, enc, out, flags));
@@ -1026,7 +1060,7 @@ int eccx_point_compress_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_xy
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_xy && d_out)) return rc;
   if ((opts & ECCX_UNCOMPRESSED) && !ops->compress_raw)
-    return arg_err(ctx, "ECCX_UNCOMPRESSED: the flavour exists for bls12_381_g1 only");
+    return arg_err(ctx, "ECCX_UNCOMPRESSED: the flavour exists for bls12_381_g1 and bls12_381_g2 only");
   HIP_TRY(ctx, ((opts & ECCX_UNCOMPRESSED) ? ops->compress_raw : ops->compress)(
                    grid(ctx, n, 8), static_cast<hipStream_t>(stream), n, static_cast<const uint8_t*>(d_xy),
                    static_cast<const uint8_t*>(d_inf), static_cast<uint8_t*>(d_out)));

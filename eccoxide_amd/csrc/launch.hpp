@@ -188,6 +188,7 @@ const CurveOps& ops_P521();
 const CurveOps& ops_BLS12_381();
 const CurveOps& ops_ED25519();
 const CurveOps& ops_P256K1();
+const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring slots (var, base, point_add are null)
 
 // curve25519 x-only ladder (k_ed25519.hip): rows of row_words<8>() = 24 words per unit
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u,

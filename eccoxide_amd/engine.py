@@ -10,8 +10,9 @@ from . import _lib
 
 # curve ids (include/eccx.h: eccx_curve)
 P256R1, P384R1, P521R1, BLS12_381_G1, ED25519, P256K1 = 0, 1, 2, 3, 4, 5
+BLS12_381_G2 = 7  # id 6 is unassigned; a G2 coordinate is an Fp2 element: field_bytes = 96 (c1 || c0), points are 192 bytes
 CURVE_IDS = {"p256r1": P256R1, "p384r1": P384R1, "p521r1": P521R1, "bls12_381_g1": BLS12_381_G1, "ed25519": ED25519,
-             "p256k1": P256K1}
+             "p256k1": P256K1, "bls12_381_g2": BLS12_381_G2}
 CURVE_NAMES = {v: k for k, v in CURVE_IDS.items()}
 
 VALIDATE_POINTS = 1 << 0

@@ -14,6 +14,7 @@ ORDERS = {
     "bls12_381_g1": "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001",
     "ed25519": "1000000000000000000000000000000014def9dea2f79cd65812631a5cf5d3ed",
     "p256k1": "fffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141",
+    "bls12_381_g2": "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001",
 }
 SEED_BASE = 0xECC051DE00000000
 

@@ -124,7 +124,19 @@ typedef enum {
   ECCX_P521R1 = 2,       /* src/curve/sec2/p521r1.rs */
   ECCX_BLS12_381_G1 = 3, /* src/curve/bls12_381/g1.rs */
   ECCX_ED25519 = 4,      /* src/curve/curve25519.rs (twisted Edwards form) */
-  ECCX_P256K1 = 5        /* src/curve/sec2/p256k1.rs (secp256k1; ECDSA: src/protocol/ecdsa.rs:466-473) */
+  ECCX_P256K1 = 5,       /* src/curve/sec2/p256k1.rs (secp256k1; ECDSA: src/protocol/ecdsa.rs:466-473) */
+  /* id 6 stays unassigned (an invalid curve id) */
+  /* src/curve/bls12_381/g2.rs: the prime-order subgroup of the twist y^2 = x^3 + 4(1 + u) over Fp2.  A coordinate is an
+   * Fp2 element c0 + c1 u of 96 bytes, c1 || c0, each component 48 bytes big-endian: eccx_field_bytes = 96, point
+   * records are n x 192 bytes (x || y), eccx_scalar_bytes = 32, eccx_compressed_bytes = 96 (zcash; ECCX_UNCOMPRESSED:
+   * 192).  Inputs may be any point of the twist; a scalar is taken as the integer its 32 bytes spell (not reduced
+   * modulo r).  Served: eccx_scalarmul_var (options none, ECCX_VALIDATE_POINTS, ECCX_CT_SCAN; ECCX_ASSUME_SUBGROUP is
+   * accepted and changes nothing), eccx_scalarmul_base (none, ECCX_CT_SCAN), eccx_point_add (ECCX_SUBTRACT),
+   * eccx_point_compress / _decompress (ECCX_UNCOMPRESSED, ECCX_CHECK_SUBGROUP), eccx_comb_table, eccx_prepare
+   * (ECCX_PREP_BASE, ECCX_PREP_CT), eccx_reserve and the _dev / _sharded forms of these.  Everything else -- proj,
+   * ECCX_MIRROR_REFERENCE, ECCX_TABLE_IN_LDS, ECCX_TABLE_IN_L2, ECCX_CT_GATHER, eccx_double_scalarmul, ECDSA -- returns
+   * ECCX_ERR_ARG. */
+  ECCX_BLS12_381_G2 = 7
 } eccx_curve;
 
 enum {

@@ -20,6 +20,7 @@ pub const ECCX_P521R1: c_int = 2;
 pub const ECCX_BLS12_381_G1: c_int = 3;
 pub const ECCX_ED25519: c_int = 4;
 pub const ECCX_P256K1: c_int = 5;
+pub const ECCX_BLS12_381_G2: c_int = 7; // 6 is unassigned
 
 // status codes
 pub const ECCX_OK: c_int = 0;

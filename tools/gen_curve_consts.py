@@ -389,6 +389,58 @@ def emit_bls_h2c(out):
     out.append("};")
 
 
+def emit_bls_g2(out):
+    """BLS12_381_G2: the twist E'(Fp2): y^2 = x^3 + 4(1 + u) in the working form of BLS12_381U (14 x 28-bit Montgomery
+    digits per component, c0 then c1): b and the real part of 3b = 12 + 12u (both components are equal), the generator,
+    the two coefficients of psi = twist o Frobenius o untwist (xi^-((p-1)/3), xi^-((p-1)/2) for xi = 1 + u, computed here
+    and pinned against the reference's bytes by tests/test_g2_cpu.py), and the two public exponents of the complex-method
+    square root."""
+    p = CURVES[3][1]
+    gx = (0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
+          0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E)
+    gy = (0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
+          0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE)
+
+    def mul(a, b):
+        return ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)
+
+    def power(a, e):
+        r = (1, 0)
+        while e:
+            if e & 1:
+                r = mul(r, a)
+            a = mul(a, a)
+            e >>= 1
+        return r
+
+    def inv(a):
+        n = pow(a[0] * a[0] + a[1] * a[1], -1, p)
+        return (a[0] * n % p, -a[1] * n % p)
+
+    # the generator is on the twist, and psi maps it to the twist
+    rhs = lambda x: tuple((c + 4) % p for c in mul(mul(x, x), x))
+    assert mul(gy, gy) == rhs(gx)
+    psi_x, psi_y = inv(power((1, 1), (p - 1) // 3)), inv(power((1, 1), (p - 1) // 2))
+    conj = lambda a: (a[0], -a[1] % p)
+    px, py = mul(conj(gx), psi_x), mul(conj(gy), psi_y)
+    assert mul(py, py) == rhs(px)
+    bits, n = 28, 14
+    R = 1 << (bits * n)
+    mont = lambda v: digits(v * R % p, bits, n)
+    out.append("")
+    out.append("struct BLS12_381_G2 {  // the twist y^2 = x^3 + 4(1 + u) over Fp2, working form of BLS12_381U")
+    out.append(arr("CB", mont(4)) + "  // b = 4 + 4u: both components")
+    out.append(arr("CB3", mont(12)) + "  // 3b = 12 + 12u: both components")
+    for name, v in (("GX", gx), ("GY", gy), ("PSI_X", psi_x), ("PSI_Y", psi_y)):
+        out.append(arr(name + "0", mont(v[0])))
+        out.append(arr(name + "1", mont(v[1])))
+    for name, e, what in (("PM3D4", (p - 3) // 4, "(p - 3) / 4"), ("PM1D2", (p - 1) // 2, "(p - 1) / 2")):
+        nw = (e.bit_length() + 31) // 32
+        out.append("  static constexpr int %s_BITS = %d;  // of %s" % (name, e.bit_length(), what))
+        out.append("  static constexpr uint32_t %s[%d] = {%s};" % (name, nw, ", ".join("0x%08xu" % ((e >> (32 * i)) & 0xFFFFFFFF) for i in range(nw))))
+    out.append("};")
+
+
 def main():
     out = ["// @generated by tools/gen_curve_consts.py -- do not edit.",
            "// Montgomery constants, 32-bit little-endian limbs, R = 2^(32*L).", ""]
@@ -470,6 +522,7 @@ def main():
     emit_field(out, ell, 8)
     out.append("};")
     emit_bls_h2c(out)
+    emit_bls_g2(out)
     sys.stdout.write("\n".join(out) + "\n")
 
 
