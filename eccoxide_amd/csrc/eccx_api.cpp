@@ -838,7 +838,9 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
   if (max_n == 0) return ECCX_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // every entry point writes un-normalised rows first; eccx_ed25519_sign runs the comb on 2 max_n lanes
-  const size_t rows = ((what & ECCX_PREP_ED25519_SIGN) && ops->ed_sign_expand) ? 2 * max_n : max_n;
+  // and eccx_hash_to_g2 clears the cofactor with a second row per unit as room
+  const size_t rows = (((what & ECCX_PREP_ED25519_SIGN) && ops->ed_sign_expand) || ((what & ECCX_PREP_H2C) && ops->h2c_clear))
+                          ? 2 * max_n : max_n;
   const Need none{0, 0};
   const bool var = (what & (ECCX_PREP_VAR | ECCX_PREP_ECDSA | ECCX_PREP_ED25519)) != 0;  // the default ladder and the verify shape
   const bool ct = (what & ECCX_PREP_CT) && ops->var_ct;                                  // the secret-scalar ladder
@@ -868,7 +870,8 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     rc = ensure_slab<EdSignSlab>(ctx, B_EDSIGN, ops, max_n, nullptr);
   if (!rc && (what & ECCX_PREP_ECDSA_SIGN) && ops->ecdsa_sign_finish)
     rc = ensure_slab<EcdsaSignSlab>(ctx, B_ECSIGN, ops, max_n, nullptr);
-  // eccx_hash_to_g1 works in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C asks for nothing more)
+  // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
+  // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
   return rc;
 }
 
@@ -1370,44 +1373,80 @@ int eccx_ed25519_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64
   return wipe_io(ctx, rc, bufs[0], nullptr, n);
 }
 
-int eccx_hash_to_g1_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
-                        void* d_out, void* d_flags, uint32_t opts, void* stream) {
+namespace {
+// eccx_hash_to_g1 and eccx_hash_to_g2 are one body: the curve decides the kernels, the record size and whether the
+// cofactor is a launch of its own (G2), which takes a second row per unit as working room.
+struct H2cWhat {
+  int curve;
+  size_t point_bytes;
+  const char* opts_msg;
+  const char* offsets_msg;
+};
+const H2cWhat H2C_G1 = {ECCX_BLS12_381_G1, 96, "eccx_hash_to_g1: opts must be 0 or ECCX_H2C_NU (the messages are public)",
+                        "eccx_hash_to_g1: the offsets decrease"};
+const H2cWhat H2C_G2 = {ECCX_BLS12_381_G2, 192, "eccx_hash_to_g2: opts must be 0 or ECCX_H2C_NU (the messages are public)",
+                        "eccx_hash_to_g2: the offsets decrease"};
+size_t h2c_rows(const CurveOps* ops, size_t n) { return ops->h2c_clear ? 2 * n : n; }
+
+int hash_to_curve_dev(eccx_ctx* ctx, const H2cWhat& w, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
+                      size_t dst_len, void* d_out, void* d_flags, uint32_t opts, void* stream) {
   if (!ctx) return ECCX_ERR_ARG;
-  if (opts & ~(uint32_t)ECCX_H2C_NU) return arg_err(ctx, "eccx_hash_to_g1: opts must be 0 or ECCX_H2C_NU (the messages are public)");
+  if (opts & ~(uint32_t)ECCX_H2C_NU) return arg_err(ctx, w.opts_msg);
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_msgs && d_offsets && d_out && d_flags && (dst || dst_len == 0))) return rc;
-  const CurveOps* ops = ops_of(ECCX_BLS12_381_G1);
+  const CurveOps* ops = ops_of(w.curve);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int count = (opts & ECCX_H2C_NU) ? 1 : 2;
+  // len_in_bytes: 64 bytes per component of a field element (m = 2 on G2)
+  const uint32_t per_element = w.curve == ECCX_BLS12_381_G2 ? 128u : 64u;
   eccx::H2cTag tag;
-  eccx::h2c_host::pack_tag(tag, dst, dst_len, 64u * (uint32_t)count);
-  if (int rc = ensure_rows(ctx, ops, n)) return rc;
+  eccx::h2c_host::pack_tag(tag, dst, dst_len, per_element * (uint32_t)count);
+  if (int rc = ensure_rows(ctx, ops, h2c_rows(ops, n))) return rc;
   uint8_t* flags = static_cast<uint8_t*>(d_flags);
   // hash_to_field into the rows; map, add, clear the cofactor in place; normalise
   HIP_TRY(ctx, ops->h2c_hash_to_field(grid(ctx, n, 8), s, n, static_cast<const uint8_t*>(d_msgs), static_cast<const uint64_t*>(d_offsets),
                                       tag, count, ctx->rows(), flags));
   HIP_TRY(ctx, ops->h2c_map_finish(ops->h2c_map_grid(ctx->cus, n), s, n, count, ctx->rows()));
+  if (ops->h2c_clear) HIP_TRY(ctx, ops->h2c_clear(ops->h2c_clear_grid(ctx->cus, n), s, n, ctx->rows()));
   HIP_TRY(ctx, ops->to_affine_var(norm_grid(ctx, n), s, n, ctx->rows(), static_cast<uint8_t*>(d_out), flags));
   return ECCX_OK;
 }
 
-int eccx_hash_to_g1(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
-                    uint8_t* out, uint8_t* flags, uint32_t opts) {
+int hash_to_curve_host(eccx_ctx* ctx, const H2cWhat& w, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                       size_t dst_len, uint8_t* out, uint8_t* flags, uint32_t opts) {
   if (!ctx) return ECCX_ERR_ARG;
-  if (opts & ~(uint32_t)ECCX_H2C_NU) return arg_err(ctx, "eccx_hash_to_g1: opts must be 0 or ECCX_H2C_NU (the messages are public)");
+  if (opts & ~(uint32_t)ECCX_H2C_NU) return arg_err(ctx, w.opts_msg);
   if (n == 0) return ECCX_OK;
   if (!offsets || !out || !flags || (!dst && dst_len != 0)) return arg_err(ctx, "null buffer");
   EdMsgs m{msgs, offsets};
-  if (int rc = m.check(ctx, n, "eccx_hash_to_g1: the offsets decrease")) return rc;
+  if (int rc = m.check(ctx, n, w.offsets_msg)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rc = m.grow_slots(ctx, n)) return rc;
-  HostBuf bufs[] = {out_buf(IO_O, out, 96), out_buf(IO_F, flags, 1)};
+  HostBuf bufs[] = {out_buf(IO_O, out, w.point_bytes), out_buf(IO_F, flags, 1)};
   return host_pipeline(
       ctx, n, bufs, /*chunked=*/true,
       [&](size_t lo, size_t cnt, uint8_t* const* d) {
-        return eccx_hash_to_g1_dev(ctx, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d[1], opts, ctx->stream);
+        return hash_to_curve_dev(ctx, w, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d[1], opts, ctx->stream);
       },
       [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
+}
+}  // namespace
+
+int eccx_hash_to_g1_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        void* d_out, void* d_flags, uint32_t opts, void* stream) {
+  return hash_to_curve_dev(ctx, H2C_G1, n, d_msgs, d_offsets, dst, dst_len, d_out, d_flags, opts, stream);
+}
+int eccx_hash_to_g1(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    uint8_t* out, uint8_t* flags, uint32_t opts) {
+  return hash_to_curve_host(ctx, H2C_G1, n, msgs, offsets, dst, dst_len, out, flags, opts);
+}
+int eccx_hash_to_g2_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        void* d_out, void* d_flags, uint32_t opts, void* stream) {
+  return hash_to_curve_dev(ctx, H2C_G2, n, d_msgs, d_offsets, dst, dst_len, d_out, d_flags, opts, stream);
+}
+int eccx_hash_to_g2(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    uint8_t* out, uint8_t* flags, uint32_t opts) {
+  return hash_to_curve_host(ctx, H2C_G2, n, msgs, offsets, dst, dst_len, out, flags, opts);
 }
 
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,

@@ -100,6 +100,7 @@ const CurveOps& ops_BLS12_381_G2() {
     t.ct_convert = table_convert_;
     t.base_ct = base_ct_;
     t.base_unsat = base_index_;
+    h2c_ops_BLS12_381_G2(t);  // hashing to G2
     return t;
   }();
   return o;

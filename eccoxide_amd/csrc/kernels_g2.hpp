@@ -22,6 +22,7 @@
 //   k_g2_point_add        a + b or a - b on affine inputs with optional infinity flags, into rows
 //   k_g2_decompress / k_g2_from_uncompressed / k_g2_compress   the zcash formats, 96 and 192 bytes
 //   k_g2_subgroup_check   psi(Q) = -[|x|]Q (g2.rs:68-122), in place behind the decoders
+//   g2_mul_seed_abs       [|x|]Q, the chain both the subgroup test and clear_cofactor (kernels_h2c_g2.hpp) walk
 #pragma once
 #include "kernels_unsat.hpp"
 #include "ufe2.hpp"
@@ -550,6 +551,49 @@ __global__ void __launch_bounds__(WG) k_g2_compress(size_t n, const uint8_t* __r
   }
 }
 
+// ---- [|x|]Q along the public seed (mul_by_abs_x of g2.rs) -----------------------------------------------------------
+// a holds the base on entry and [|x|] base on return: 63 doublings and 5 complete additions of the base, which is an
+// affine entry (the mixed form), a projective point, or a row of the result buffer read again at each of the five
+// additions so that only the accumulator stays in registers through the doublings.  S: the struct with SEED_ABS.
+struct G2RowRef {
+  const uint32_t* row;
+};
+template <class C>
+ECCX_DEV void g2_add_base(G2Pt<C>& r, const G2Pt<C>& a, const G2Aff<C>& q) { g2_madd<C>(r, a, q); }
+template <class C>
+ECCX_DEV void g2_add_base(G2Pt<C>& r, const G2Pt<C>& a, const G2Pt<C>& q) { g2_add<C>(r, a, q); }
+template <class C>
+ECCX_DEV void g2_add_base(G2Pt<C>& r, const G2Pt<C>& a, const G2RowRef& q) {
+  G2Pt<C> b;
+  g2_row_load<C>(b, q.row);
+  g2_add<C>(r, a, b);
+}
+template <class C, class S, class Base>
+ECCX_DEV void g2_mul_seed_abs(G2Pt<C>& a, const Base& q) {
+  static_assert((S::SEED_ABS >> 63) == 1, "the chain starts from the top bit of |x|");
+#pragma nounroll
+  for (int i = 62; i >= 0; --i) {
+    G2Pt<C> t;
+    g2_dbl<C>(t, a);
+    a = t;
+    if ((S::SEED_ABS >> i) & 1) {  // wave-uniform: the seed is a constant
+      g2_add_base<C>(t, a, q);
+      a = t;
+    }
+  }
+}
+// psi on a projective point: (conj(X) PSI_X : conj(Y) PSI_Y : conj(Z)); infinity stays infinity
+template <class C, class G>
+ECCX_DEV void g2_psi(G2Pt<C>& r, const G2Pt<C>& p) {
+  r.x = f2_fit<1, 3>(f2_mul(f2_conj(p.x), f2_const<C>(G::PSI_X0, G::PSI_X1)));
+  r.y = f2_fit<1, 3>(f2_mul(f2_conj(p.y), f2_const<C>(G::PSI_Y0, G::PSI_Y1)));
+  r.z = f2_reduce(f2_conj(p.z));
+}
+template <class C>
+ECCX_DEV void g2_negate(G2Pt<C>& p) {
+  p.y = f2_reduce(f2_neg(p.y));
+}
+
 // ---- subgroup membership (g2.rs:68-122) -----------------------------------------------------------------------------
 // Q in G2  <=>  psi(Q) = [x]Q = -[|x|]Q, psi(x, y) = (conj(x) PSI_X, conj(y) PSI_Y).  [|x|]Q follows the public seed:
 // 63 doublings and 5 mixed complete additions; the comparison is projective: with A = [|x|]Q = (X : Y : Z),
@@ -567,16 +611,7 @@ __global__ void __launch_bounds__(WG, 1) k_g2_subgroup_check(size_t n, uint8_t* 
     (void)g2_load_affine<C>(q, xy + idx * (size_t)PB);
     G2Pt<C> a;
     a.x = q.x; a.y = q.y; a.z = f2_one<C>();
-#pragma nounroll
-    for (int i = 62; i >= 0; --i) {
-      G2Pt<C> t;
-      g2_dbl<C>(t, a);
-      a = t;
-      if ((S::SEED_ABS >> i) & 1) {  // wave-uniform: the seed is a constant
-        g2_madd<C>(t, a, q);
-        a = t;
-      }
-    }
+    g2_mul_seed_abs<C, S>(a, q);
     const U2<C, 1, 3> px = f2_fit<1, 3>(f2_mul(f2_conj(q.x), f2_const<C>(G::PSI_X0, G::PSI_X1)));
     const U2<C, 1, 3> py = f2_fit<1, 3>(f2_mul(f2_conj(q.y), f2_const<C>(G::PSI_Y0, G::PSI_Y1)));
     const bool finite = !f2_is_zero(a.z);

@@ -3,7 +3,7 @@
 //   g1::Point::hash_to_curve / encode_to_curve        src/curve/bls12_381/g1.rs:181-201
 //   expand_message_xmd, hash_to_field, the maps       src/curve/bls12_381/hash_to_curve.rs
 //
-//   expand_message_xmd<ELL>   32 ELL uniform bytes from a message and the call's tag (h2c_tag.hpp)
+//   expand_message_xmd<ELL>   32 ELL uniform bytes from a message and the call's tag (h2c_tag.hpp), ELL <= 8
 //   h2c_fp_from_uniform       64 big-endian bytes -> the element mod p, working form
 //   h2c_map_to_curve_g1       Simplified SWU onto E' (straight-line form, x kept as a fraction), then the 11-isogeny
 //                             evaluated homogeneously: no inversion; the result is a Jacobian point
@@ -23,12 +23,12 @@
 namespace eccx {
 
 // ---- expand_message_xmd ----------------------------------------------------------------------------------------------
-// out: 8 ELL big-endian words.  b0_tail: the tag's b0_tail where every lane can index it (LDS); len_in_bytes is part of
-// the tag, and ELL must be its number of blocks.
-template <int ELL>
-ECCX_DEV void expand_message_xmd(uint32_t (&out)[8 * ELL], const uint8_t* msg, uint64_t len, const H2cTag& tag,
-                                 const uint32_t* b0_tail) {
-  static_assert(ELL >= 1 && ELL <= 4, "blocks of output");
+// ELL blocks of 32 uniform bytes from a message and the call's tag, each handed to emit(i, h) as it is produced: i counts
+// from 0 and is a constant once the loop is unrolled, h holds the block's 8 big-endian words.  b0_tail: the tag's b0_tail
+// where every lane can index it (LDS); len_in_bytes is part of the tag, and ELL must be its number of blocks.
+template <int ELL, class Emit>
+ECCX_DEV void expand_message_xmd_blocks(const uint8_t* msg, uint64_t len, const H2cTag& tag, const uint32_t* b0_tail, Emit&& emit) {
+  static_assert(ELL >= 1 && ELL <= 8, "blocks of output");
   uint32_t b0[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) b0[j] = SHA256_ZERO_BLOCK.h[j];
@@ -50,11 +50,18 @@ ECCX_DEV void expand_message_xmd(uint32_t (&out)[8 * ELL], const uint8_t* msg, u
       sha256_compress(h, w);
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      prev[j] = h[j];
-      out[8 * (i - 1) + j] = h[j];
-    }
+    for (int j = 0; j < 8; ++j) prev[j] = h[j];
+    emit(i - 1, h);
   }
+}
+// out: 8 ELL big-endian words
+template <int ELL>
+ECCX_DEV void expand_message_xmd(uint32_t (&out)[8 * ELL], const uint8_t* msg, uint64_t len, const H2cTag& tag,
+                                 const uint32_t* b0_tail) {
+  expand_message_xmd_blocks<ELL>(msg, len, tag, b0_tail, [&](int i, const uint32_t (&h)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[8 * i + j] = h[j];
+  });
 }
 
 // ---- 512 bits -> Fp ----------------------------------------------------------------------------------------------------

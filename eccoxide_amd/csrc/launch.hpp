@@ -160,14 +160,18 @@ struct CurveOps {
                                   const uint8_t* nonces, const uint8_t* xs, const uint8_t* lflags, uint8_t* sigs, uint8_t* status);
   hipError_t (*ecdsa_pubkey_finish)(int grid, hipStream_t s, size_t n, const uint8_t* secrets, const uint8_t* lflags, uint8_t* out,
                                     int width, uint8_t* status);
-  // Hashing to the curve (kernels_h2c.hpp; bls12_381_g1 only, else null).  h2c_hash_to_field hashes the messages (as
-  // ed_verify_prepare takes them) under the call's tag to `count` field elements per unit (1: encode_to_curve, 2:
-  // hash_to_curve), parked in the unit's result row, and writes flags 0, or 2 for a lane whose offsets decrease.
-  // h2c_map_finish maps them to the curve, adds, clears the cofactor and leaves (X, Y, Z) in the row for to_affine_var.
+  // Hashing to the curve (kernels_h2c.hpp, kernels_h2c_g2.hpp; bls12_381_g1 and bls12_381_g2, else null).
+  // h2c_hash_to_field hashes the messages (as ed_verify_prepare takes them) under the call's tag to `count` field
+  // elements per unit (1: encode_to_curve, 2: hash_to_curve), parked in the unit's result row, and writes flags 0, or 2
+  // for a lane whose offsets decrease.  h2c_map_finish maps them to the curve and adds; on G1 it clears the cofactor as
+  // well and leaves (X, Y, Z) in the row for to_affine_var.  On G2 the cofactor is a launch of its own, h2c_clear (null
+  // on G1), which works in place on rows 0 .. n and needs rows n .. 2n as room.
   hipError_t (*h2c_hash_to_field)(int grid, hipStream_t s, size_t n, const uint8_t* msgs, const uint64_t* offsets, const H2cTag& tag,
                                   int count, uint32_t* rows, uint8_t* flags);
   hipError_t (*h2c_map_finish)(int grid, hipStream_t s, size_t n, int count, uint32_t* rows);
   int (*h2c_map_grid)(int cus, size_t n);
+  hipError_t (*h2c_clear)(int grid, hipStream_t s, size_t n, uint32_t* rows);
+  int (*h2c_clear_grid)(int cus, size_t n);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
@@ -189,6 +193,7 @@ const CurveOps& ops_BLS12_381();
 const CurveOps& ops_ED25519();
 const CurveOps& ops_P256K1();
 const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring slots (var, base, point_add are null)
+void h2c_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_h2c.hip: the h2c_* slots of ops_BLS12_381_G2
 
 // curve25519 x-only ladder (k_ed25519.hip): rows of row_words<8>() = 24 words per unit
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u,

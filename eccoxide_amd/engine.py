@@ -154,7 +154,7 @@ class Engine:
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
         row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key; h2c: the row buffer
-        hash_to_g1 works in (curve "bls12_381_g1")."""
+        hash_to_g1 works in (curve "bls12_381_g1") or hash_to_g2 (curve "bls12_381_g2": two rows per unit)."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
@@ -439,6 +439,14 @@ class Engine:
         """Hash a batch of messages to BLS12-381 G1 (eccx_hash_to_g1; RFC 9380, g1::Point::hash_to_curve): messages is a
         list of n byte strings, dst the domain separation tag of the call (any length).  nonuniform selects
         encode_to_curve (the ..._NU_ suite).  Returns (points n x 96 affine x || y, flags n)."""
+        return self._hash_to(self._lib.eccx_hash_to_g1, 96, messages, dst, nonuniform)
+
+    def hash_to_g2(self, messages, dst: bytes, *, nonuniform: bool = False):
+        """Hash a batch of messages to BLS12-381 G2 (eccx_hash_to_g2; RFC 9380, g2::Point::hash_to_curve), as hash_to_g1.
+        Returns (points n x 192 affine x || y, each coordinate c1 || c0, flags n)."""
+        return self._hash_to(self._lib.eccx_hash_to_g2, 192, messages, dst, nonuniform)
+
+    def _hash_to(self, fn, width, messages, dst, nonuniform):
         import numpy as np
 
         n = len(messages)
@@ -446,11 +454,11 @@ class Engine:
         np.cumsum([len(m) for m in messages], out=offsets[1:])
         msgs = b"".join(bytes(m) for m in messages)
         dst = bytes(dst)
-        out = ctypes.create_string_buffer(max(1, 96 * n))
+        out = ctypes.create_string_buffer(max(1, width * n))
         flags = ctypes.create_string_buffer(max(1, n))
-        self._check(self._lib.eccx_hash_to_g1(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, dst if dst else None,
-                                              len(dst), out, flags, H2C_NU if nonuniform else 0))
-        return out.raw[:96 * n], flags.raw[:n]
+        self._check(fn(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, dst if dst else None, len(dst), out, flags,
+                       H2C_NU if nonuniform else 0))
+        return out.raw[:width * n], flags.raw[:n]
 
     def hash_to_g1_t(self, msgs, offsets, dst: bytes, out=None, flags=None, *, nonuniform: bool = False,
                      stream: Optional[int] = None, check_bounds: bool = True):
@@ -458,6 +466,15 @@ class Engine:
         Enqueued on `stream` (default: torch's current stream); returns (points n x 96, flags n) tensors -- what
         scalarmul_var_t and point_compress_t take.  A lane whose offsets decrease is flagged FLAG_REJECTED.  check_bounds
         as in ed25519_verify_t."""
+        return self._hash_to_t(self._lib.eccx_hash_to_g1_dev, 96, msgs, offsets, dst, out, flags, nonuniform, stream, check_bounds)
+
+    def hash_to_g2_t(self, msgs, offsets, dst: bytes, out=None, flags=None, *, nonuniform: bool = False,
+                     stream: Optional[int] = None, check_bounds: bool = True):
+        """Device-tensor form of hash_to_g2 (eccx_hash_to_g2_dev), as hash_to_g1_t; returns (points n x 192, flags n)
+        tensors -- what scalarmul_var_t, point_compress_t and point_add_t take for "bls12_381_g2"."""
+        return self._hash_to_t(self._lib.eccx_hash_to_g2_dev, 192, msgs, offsets, dst, out, flags, nonuniform, stream, check_bounds)
+
+    def _hash_to_t(self, fn, width, msgs, offsets, dst, out, flags, nonuniform, stream, check_bounds):
         import torch
 
         n = offsets.numel() - 1
@@ -466,10 +483,10 @@ class Engine:
         if not offsets.is_cuda or not msgs.is_cuda or msgs.dtype != torch.uint8 or not msgs.is_contiguous():
             raise ValueError("msgs (contiguous uint8) and offsets must be CUDA tensors")
         if out is None:
-            out = torch.empty((n, 96), dtype=torch.uint8, device=offsets.device)
+            out = torch.empty((n, width), dtype=torch.uint8, device=offsets.device)
         if flags is None:
             flags = torch.empty((n,), dtype=torch.uint8, device=offsets.device)
-        self._tensors(n, ("out", out, 96), ("flags", flags, 1))
+        self._tensors(n, ("out", out, width), ("flags", flags, 1))
         for name, t in (("msgs", msgs), ("offsets", offsets)):
             if t.device.index != self.device:
                 raise ValueError(f"{name}: tensor lives on cuda:{t.device.index}, this engine is bound to cuda:{self.device}")
@@ -483,8 +500,8 @@ class Engine:
         if msgs.numel() == 0:  # every message empty: any valid address
             msgs = torch.zeros((1,), dtype=torch.uint8, device=offsets.device)
         dst = bytes(dst)
-        self._check(self._lib.eccx_hash_to_g1_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None, len(dst),
-                                                  out.data_ptr(), flags.data_ptr(), H2C_NU if nonuniform else 0, stream))
+        self._check(fn(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None, len(dst), out.data_ptr(),
+                       flags.data_ptr(), H2C_NU if nonuniform else 0, stream))
         return out, flags
 
     def ed25519_public_key(self, seeds: bytes, *, ct_gather: bool = False) -> bytes:

@@ -27,6 +27,9 @@
  *   eccx_hash_to_g1[_dev]        g1::Point::hash_to_curve / encode_to_curve   src/curve/bls12_381/g1.rs:181-201
  *                              -> expand_message_xmd, hash_to_field, map_to_curve_g1   src/curve/bls12_381/hash_to_curve.rs:77-134,
  *                              :454-520; clear_cofactor g1.rs:131-134
+ *   eccx_hash_to_g2[_dev]        g2::Point::hash_to_curve / encode_to_curve   src/curve/bls12_381/g2.rs:218-238
+ *                              -> hash_to_field_g2, map_to_curve_g2, the any-field sqrt_ratio   hash_to_curve.rs:255-305,
+ *                              :501-529; clear_cofactor g2.rs:161-171
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
@@ -87,11 +90,14 @@
  * eccx_hash_to_g1 treats its messages as PUBLIC and makes no secret-data promise.  The reference's map is branch-free
  * (hash_to_curve.rs:325-350); ours resolves the map's own cases by selects as well, but a lane's SHA-256 block count
  * follows its message length, and the additions behind the map take wave-uniform branches on Q0 = +-Q1.
+ * eccx_hash_to_g2 likewise: public messages, no secret-data promise.  Its map resolves its cases by selects and its
+ * additions are the complete formulas, so what follows the data is the SHA-256 block count of a lane alone.
  *
  * MEMORY AND BLOCKING.  A context is bound to one GPU and owns
  *   - the window-table slab of the variable-base ladders: resident lanes x 17 rows (P-256:
  *     0.86 GB, p256k1 as P-256, P-384 / BLS12-381: 0.62 GB, P-521: 0.79 GB; sized by the largest batch seen),
- *   - a buffer of un-normalised result rows, 112-224 bytes per unit of the largest batch seen,
+ *   - a buffer of un-normalised result rows, 112-224 bytes per unit of the largest batch seen (bls12_381_g2: 336, and two
+ *     such rows per unit for eccx_hash_to_g2),
  *   - the fixed-base tables of each curve used: the 16-bit-window table (134 MB for p256r1,
  *     ed25519, bls12_381_g1 and p256k1, 201 MB p384r1, 415 MB p521r1), the reference-layout comb
  *     (64-265 KB), for ECCX_TABLE_IN_LDS a 155 KB image, for ECCX_CT_SCAN / ECCX_CT_GATHER a signed-window
@@ -192,8 +198,9 @@ enum {
   ECCX_OUT_X_ONLY = 1u << 11,      /* eccx_double_scalarmul: write the x-coordinate alone, FB bytes per unit (`out` is then
                                       n x FB): Point::to_affine_x_ct (src/curve/projective.rs:690), which is all ECDSA
                                       verification reads (src/protocol/ecdsa.rs:383).  Weierstrass curves. */
-  ECCX_H2C_NU = 1u << 13,          /* eccx_hash_to_g1: the nonuniform suite BLS12381G1_XMD:SHA-256_SSWU_NU_ (encode_to_curve:
-                                      one field element, one map) instead of ..._RO_ (hash_to_curve) */
+  ECCX_H2C_NU = 1u << 13,          /* eccx_hash_to_g1, eccx_hash_to_g2: the nonuniform suite BLS12381G1_XMD:SHA-256_SSWU_NU_
+                                      (BLS12381G2_...; encode_to_curve: one field element, one map) instead of ..._RO_
+                                      (hash_to_curve) */
   ECCX_ASSUME_SUBGROUP = 1u << 9   /* eccx_scalarmul_var, bls12_381_g1: the caller guarantees every base point
                                       is in the prime-order subgroup G1 (e.g. it was decoded under
                                       ECCX_CHECK_SUBGROUP, or is a multiple of the generator).  The
@@ -224,7 +231,8 @@ enum {
                                    output and flags) and the fixed-base row buffer */
   ECCX_PREP_H2C = 1u << 11,     /* eccx_reserve (bls12_381_g1): the result-row buffer eccx_hash_to_g1 works in (it has no other
                                    slab); with ECCX_PREP_HOST the copies of the host form's points and flags -- its message
-                                   slot grows on demand, as Ed25519's does */
+                                   slot grows on demand, as Ed25519's does.  bls12_381_g2: the same for eccx_hash_to_g2,
+                                   whose cofactor chain takes a second row per unit (2 x 336 bytes) */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -464,6 +472,24 @@ int eccx_ed25519_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const voi
 int eccx_hash_to_g1(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
                     uint8_t* out, uint8_t* flags, uint32_t opts);
 int eccx_hash_to_g1_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        void* d_out, void* d_flags, uint32_t opts, void* stream);
+
+/* Hashing to BLS12-381 G2, batched (RFC 9380 8.8.2; g2::Point::hash_to_curve / encode_to_curve, src/curve/bls12_381/g2.rs:
+ * 218-238): H(m) of the min-pk BLS signature scheme, whose signatures live in G2.  The contract is eccx_hash_to_g1's, point
+ * for point -- msgs, offsets, dst, dst_len, flags, the errors, n == 0, and what the _dev form promises after eccx_reserve
+ * (ECCX_BLS12_381_G2, max_n, ECCX_PREP_H2C) -- with these differences:
+ *   out           : n x 192, affine x || y, each coordinate c1 || c0 big-endian -- the record eccx_scalarmul_var[_dev],
+ *                   eccx_point_compress[_dev] and eccx_point_add[_dev] take for ECCX_BLS12_381_G2, so hash -> sk * H(m)
+ *                   (ECCX_CT_SCAN) -> compress stays on the GPU
+ *   flags         : 0: a point of G2; ECCX_FLAG_INFINITY and ECCX_FLAG_REJECTED as for G1
+ *   opts          : 0 selects BLS12381G2_XMD:SHA-256_SSWU_RO_, ECCX_H2C_NU selects ..._NU_; anything else is ECCX_ERR_ARG
+ * On the GPU, all of it: expand_message_xmd to 256 (128) bytes, four (two) reductions of 64 bytes mod p, Simplified SWU
+ * over Fp2 onto the 3-isogenous curve with the any-field sqrt_ratio (RFC 9380 F.2.1.1), the isogeny, Q0 + Q1, the
+ * endomorphism chain psi^2(2Q) + [x]([x]Q + psi(Q)) - [x]Q - psi(Q) - Q (multiplication by h_eff), then the
+ * normalisation.  The result-row buffer holds two rows per unit here. */
+int eccx_hash_to_g2(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    uint8_t* out, uint8_t* flags, uint32_t opts);
+int eccx_hash_to_g2_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
                         void* d_out, void* d_flags, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.

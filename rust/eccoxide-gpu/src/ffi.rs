@@ -43,7 +43,7 @@ pub const ECCX_ASSUME_SUBGROUP: u32 = 1 << 9;
 pub const ECCX_CT_GATHER: u32 = 1 << 10;
 pub const ECCX_OUT_X_ONLY: u32 = 1 << 11;
 pub const ECCX_PUBKEY_SEC1: u32 = 1 << 12;
-pub const ECCX_H2C_NU: u32 = 1 << 13; // eccx_hash_to_g1: encode_to_curve (the ..._NU_ suite)
+pub const ECCX_H2C_NU: u32 = 1 << 13; // eccx_hash_to_g1 / _g2: encode_to_curve (the ..._NU_ suite)
 
 // eccx_prepare / eccx_reserve
 pub const ECCX_PREP_VAR: u32 = 1 << 0;
@@ -59,7 +59,7 @@ pub const ECCX_PREP_ECDSA: u32 = 1 << 7; // eccx_ecdsa_verify's working slabs
 pub const ECCX_PREP_ED25519: u32 = 1 << 8; // eccx_ed25519_verify's working slab
 pub const ECCX_PREP_ED25519_SIGN: u32 = 1 << 9; // eccx_ed25519_sign's working slab, rows for 2 * max_n lanes
 pub const ECCX_PREP_ECDSA_SIGN: u32 = 1 << 10; // eccx_ecdsa_sign's / eccx_ecdsa_public_key's working slab
-pub const ECCX_PREP_H2C: u32 = 1 << 11; // eccx_hash_to_g1's result rows
+pub const ECCX_PREP_H2C: u32 = 1 << 11; // eccx_hash_to_g1's / eccx_hash_to_g2's result rows
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -154,6 +154,11 @@ extern "C" {
     pub fn eccx_hash_to_g1(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8, dst_len: usize,
                            out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
     pub fn eccx_hash_to_g1_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8,
+                               dst_len: usize, d_out: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    // hashing to BLS12-381 G2, batched                      g2::Point::hash_to_curve / encode_to_curve
+    pub fn eccx_hash_to_g2(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8, dst_len: usize,
+                           out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_hash_to_g2_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8,
                                dst_len: usize, d_out: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
 
     // X25519 over a batch                                    protocol::x25519::x25519

@@ -4,9 +4,10 @@
 
 Self-contained (standard SEC 2 / BLS12-381 / RFC 8032 constants, plain big-int
 math); does not import oracle/ or read /root/reference.  tests/ cross-check the
-generated values against tests/golden/params.json.  The one input is tests/golden/bls_h2c.json:
-RFC 9380's constants for hashing to BLS12-381 G1 (section 8.8.1, appendix E.2), checked here
-for what makes them the right constants before they are emitted.
+generated values against tests/golden/params.json.  The inputs are tests/golden/bls_h2c.json and
+tests/golden/bls_h2c_g2.json: RFC 9380's constants for hashing to BLS12-381 G1 and G2 (sections
+8.8.1 and 8.8.2, appendices E.2 and E.3), checked here for what makes them the right constants
+before they are emitted.
 
     python tools/gen_curve_consts.py > eccoxide_amd/csrc/curve_consts.inc
 """
@@ -441,6 +442,102 @@ def emit_bls_g2(out):
     out.append("};")
 
 
+def emit_bls_g2_h2c(out):
+    """BLS12_381_G2_H2C: the constants of hash_to_curve / encode_to_curve for G2 (kernels_h2c_g2.hpp) in the working form
+    of BLS12_381U, each Fp2 element as its c0 digits then its c1 digits: the isogenous curve E': y^2 = x^3 + A'x + B'
+    with A' = 240u, B' = 1012(1 + u), Z = -(2 + u), the exponent c3 and the constants c6, c7 of the any-field sqrt_ratio
+    (appendix F.2.1.1; q = p^2 = 9 mod 16, c1 = 3), and the 3-isogeny's four polynomials (appendix E.3; ascending, the
+    denominators monic, leading 1 not stored).  The one input is tests/golden/bls_h2c_g2.json, checked here for what makes
+    these the right constants before they are emitted."""
+    p = CURVES[3][1]
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "bls_h2c_g2.json")
+    with open(path) as f:
+        c = json.load(f)["constants"]
+
+    def fe(h):  # hex of c1 || c0
+        raw = bytes.fromhex(h)
+        assert len(raw) == 96
+        v = (int.from_bytes(raw[48:], "big"), int.from_bytes(raw[:48], "big"))
+        assert v[0] < p and v[1] < p
+        return v
+
+    def mul(a, b):
+        return ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)
+
+    def add(a, b):
+        return ((a[0] + b[0]) % p, (a[1] + b[1]) % p)
+
+    def power(a, e):
+        r = (1, 0)
+        while e:
+            if e & 1:
+                r = mul(r, a)
+            a = mul(a, a)
+            e >>= 1
+        return r
+
+    def inv(a):
+        n = pow(a[0] * a[0] + a[1] * a[1], -1, p)
+        return (a[0] * n % p, -a[1] * n % p)
+
+    def is_square(a):  # by the norm
+        n = (a[0] * a[0] + a[1] * a[1]) % p
+        return n == 0 or pow(n, (p - 1) // 2, p) == 1
+
+    ia, ib, z, c6, c7 = (fe(c[k]) for k in ("iso_a", "iso_b", "z", "c6", "c7"))
+    c3 = int(c["c3"], 16)
+    polys = {k: [fe(h) for h in c[k]] for k in ("k1", "k2", "k3", "k4")}
+    q = p * p
+    assert ia == (0, 240) and ib == (1012, 1012) and z == (p - 2, p - 1)
+    assert (q - 1) % 16 == 8, "c1 = 3"
+    assert c3 == ((q - 1) // 8 - 1) // 2, "c3"
+    assert c6 == power(z, (q - 1) // 8), "c6"
+    assert c7 == power(z, ((q - 1) // 8 + 1) // 2), "c7"
+    assert not is_square(z), "Z is a square"
+    assert [len(polys[k]) for k in ("k1", "k2", "k3", "k4")] == [4, 2, 4, 3], "degrees of the 3-isogeny"
+
+    def ev(co, x, monic):
+        acc = (1, 0) if monic else (0, 0)
+        for v in reversed(co):
+            acc = add(mul(acc, x), v)
+        return acc
+
+    rng = random.Random(9380)
+    while True:  # one random point of E' lands on the twist y^2 = x^3 + 4(1 + u)
+        x = (rng.randrange(p), rng.randrange(p))
+        g = add(add(mul(mul(x, x), x), mul(ia, x)), ib)
+        if not is_square(g):
+            continue
+        # a root by the complex method (p = 3 mod 4)
+        a1 = power(g, (p - 3) // 4)
+        alpha, x0 = mul(mul(a1, a1), g), mul(a1, g)
+        y = mul(x0, (0, 1)) if alpha == (p - 1, 0) else mul(power(add((1, 0), alpha), (p - 1) // 2), x0)
+        assert mul(y, y) == g
+        xd, yd = ev(polys["k2"], x, True), ev(polys["k4"], x, True)
+        if xd == (0, 0) or yd == (0, 0):
+            continue
+        X = mul(ev(polys["k1"], x, False), inv(xd))
+        Y = mul(mul(y, ev(polys["k3"], x, False)), inv(yd))
+        assert mul(Y, Y) == add(mul(mul(X, X), X), (4, 4)), "the isogeny misses the twist"
+        break
+    bits, n = 28, 14
+    R = 1 << (bits * n)
+    mont = lambda v: digits(v * R % p, bits, n)
+    out.append("")
+    out.append("struct BLS12_381_G2_H2C {  // RFC 9380 8.8.2 / E.3: hashing to G2, working form of BLS12_381U, c0 then c1")
+    for name, v in (("A", ia), ("B", ib), ("Z", z), ("C6", c6), ("C7", c7)):
+        out.append(arr(name + "0", mont(v[0])))
+        out.append(arr(name + "1", mont(v[1])))
+    out.append(arr("R2_256", digits((1 << 256) * R * R % p, bits, n)) + "  // 2^256 R^2: a * R2_256 / R = a 2^256 R")
+    for k, name in (("k1", "XNUM"), ("k2", "XDEN"), ("k3", "YNUM"), ("k4", "YDEN")):
+        out.append(arr2(name + "0", [mont(v[0]) for v in polys[k]]))
+        out.append(arr2(name + "1", [mont(v[1]) for v in polys[k]]))
+    nw = (c3.bit_length() + 31) // 32
+    out.append("  static constexpr int C3_BITS = %d;  // of c3 = ((p^2 - 1) / 8 - 1) / 2" % c3.bit_length())
+    out.append("  static constexpr uint32_t C3[%d] = {%s};" % (nw, ", ".join("0x%08xu" % ((c3 >> (32 * i)) & 0xFFFFFFFF) for i in range(nw))))
+    out.append("};")
+
+
 def main():
     out = ["// @generated by tools/gen_curve_consts.py -- do not edit.",
            "// Montgomery constants, 32-bit little-endian limbs, R = 2^(32*L).", ""]
@@ -523,6 +620,7 @@ def main():
     out.append("};")
     emit_bls_h2c(out)
     emit_bls_g2(out)
+    emit_bls_g2_h2c(out)
     sys.stdout.write("\n".join(out) + "\n")
 
 
