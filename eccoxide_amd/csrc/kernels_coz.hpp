@@ -455,6 +455,11 @@ constexpr int coz_full_windows() {
 #ifndef ECCX_COZ_OCC_U9
 #define ECCX_COZ_OCC_U9 4
 #endif
+// The public ladder without endomorphism as nested loops (windows around doublings); 0 builds it as the one loop the
+// endomorphism ladders keep, for same-box A/B.
+#ifndef ECCX_COZ_NESTED_LADDER
+#define ECCX_COZ_NESTED_LADDER 1
+#endif
 template <class CU, bool GLV>
 constexpr int coz_occupancy() {
   return CU::N <= 9 ? ECCX_COZ_OCC_U9
@@ -466,8 +471,11 @@ constexpr int coz_occupancy() {
 // leaves its zeta in LDS ([limb][thread]: conflict-free); per iteration of the grid-stride loop one wave, the duty wave,
 // multiplies the four values of threads c, 64 + c, 128 + c, 192 + c, inverts the product (fe_inv_gcd: 23 k of a
 // P-256 unit's 454 k vector instructions) and back-substitutes the four inverses: 9 products for 3 inversions saved.
-// The duty rotates over the iterations, so every wave inverts once in four (a rotation that also starts at another wave
-// in every workgroup measured no different: DESIGN.md 3.9).  The secret-scalar ladders keep one inversion per lane.
+// The duty rotates over the iterations, so every wave inverts once in four.  The four workgroups of a CU reach the
+// inversion together, and their duty waves, wave iter & 3 of each, sit on four different SIMDs as they stand: the
+// dispatcher starts every workgroup of a CU on another SIMD (tools/ubench/wg_placement.hip), which is
+// why a rotation that also starts at another wave in every workgroup measured no different.  The secret-scalar
+// ladders keep one inversion per lane.
 // The public ladder without endomorphism aligns its windows to the TOP of the 8 SB + 1 Booth positions
 // (booth_digit_aligned): the short window -- S = (8 SB + 1) mod WB positions: P-256 2, P-384 0, P-521 4 -- is then the
 // bottom one, which costs S doublings, where a short top window costs the WB doublings below it all the same.
@@ -811,10 +819,7 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         }
       }
     } else {
-      // sub 0..nd-1: doublings, nd: addition (nd+1: second half's addition); nd = WB but for the bottom window of the
-      // top-aligned form (win = -1), which has S
       constexpr int WIN_END = S != 0 ? -1 : 0;
-      int win, sub;
       {
         // the top window's (first) addition has nothing to add to: the accumulator starts as that signed
         // entry -- affine, so Z = 1 -- or at infinity for digit 0
@@ -829,6 +834,85 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
         q.y = u_reduce(sy);
         q.z = u_as<UJac<CU>::ZK, UJac<CU>::ZV>(one);
         if (d == 0) u_set_zero(q.z);
+      }
+      // q = 2 q; fix: the equal-points fix-up after an addition, only the lanes with fix_lane take the double
+      bool fix_lane = false;
+      auto dbl_step = [&](bool fix) __attribute__((always_inline)) {
+        UJac<CU> t;
+        if constexpr (UBS<CU>::DENSE) {
+          // P-256: the merged doubling, and the equal-points fix-up in a wave-uniform branch of its own.  Its
+          // selects are asm (u_cmov_ct), which the compiler does not hoist, so the common path is q = t (written
+          // with ?:, the branch is if-converted into 3 N v_cndmask that every doubling runs).
+          ujac_dbl_merged<CU>(t, q);
+          if (fix) {
+            const uint64_t keep = ct_mask(!fix_lane);  // lanes without the fix-up keep q
+            u_cmov_ct(t.x, keep, q.x);
+            u_cmov_ct(t.y, keep, q.y);
+            u_cmov_ct(t.z, keep, q.z);
+          }
+          q = t;
+        } else {
+          ujac_dbl<CU>(t, q);
+          if (fix) {
+            u_select(q.x, fix_lane, t.x, q.x);
+            u_select(q.y, fix_lane, t.y, q.y);
+            u_select(q.z, fix_lane, t.z, q.z);
+          } else {
+            q = t;
+          }
+        }
+      };
+      // q += the signed entry of window win (half `second` with GLV); sets fix_lane where q == entry, which keeps q
+      // and needs a doubling: returns whether any lane of the wave does
+      auto add_step = [&](int win, bool second) __attribute__((always_inline)) -> bool {
+        uint32_t d;
+        bool neg;
+        booth(win, second, d, neg);
+        if (second && !LATTICE) neg = !neg;  // BLS12-381: [x^2]P = -sigma(P) = (beta x, -y)
+        T ex, ey;
+        if constexpr (GLV) {
+          T eb;
+          u3_load<CU>(ex, ey, eb, row(d ? d : 1));
+          if (second) ex = eb;
+        } else {
+          u2_load<CU>(ex, ey, row(d ? d : 1));
+        }
+        const bool q_inf = u_limbs_all_zero(q.z);
+        const bool e_skip = (d == 0);
+        UJac<CU> sum;
+        bool hz, rz;
+        ujac_madd_signed<CU>(sum, hz, rz, q, ex, ey, neg);
+        const bool same_x = hz && !q_inf && !e_skip;
+        fix_lane = same_x && rz;  // q == entry: needs a doubling
+        if (same_x && !rz) u_set_zero(sum.z);  // q == -entry
+        if (__builtin_amdgcn_ballot_w64(q_inf) != 0) {  // accumulator at infinity: the sum is the entry
+          U<CU, 2, 4> sy;
+          u_select(sy, neg, u_neg(ey), u_as<2, 4>(ey));
+          u_select(sum.x, q_inf, ex, sum.x);
+          u_select(sum.y, q_inf, u_reduce(sy), sum.y);
+          u_select(sum.z, q_inf, u_as<UJac<CU>::ZK, UJac<CU>::ZV>(one), sum.z);
+        }
+        const bool keep = e_skip || fix_lane;
+        u_select(q.x, keep, q.x, sum.x);
+        u_select(q.y, keep, q.y, sum.y);
+        u_select(q.z, keep, q.z, sum.z);
+        return __builtin_amdgcn_ballot_w64(fix_lane) != 0;
+      };
+      if constexpr (!GLV && ECCX_COZ_NESTED_LADDER) {
+        // per window nd doublings, one addition and, rarely, the fix-up doubling: nd = WB but for the bottom window
+        // of the top-aligned form (win = -1), which has S.  The doublings are a loop of their own, so that its back
+        // edge carries q alone and the new coordinates are written over the old ones: one loop around a doubling OR
+        // an addition met at a back edge that copied the whole point (27 v_mov_b32 on P-256) on every step.
+#pragma unroll 1
+        for (int win = NWIN_MAIN - 2; win >= WIN_END; --win) {
+          const int nd = (S != 0 && win < 0) ? S : WB;
+#pragma unroll 1
+          for (int sub = 0; sub < nd; ++sub) dbl_step(false);
+          if (add_step(win, false)) dbl_step(true);
+        }
+      } else {
+        // one loop for both bodies: sub 0..nd-1: doublings, nd: addition (nd+1: second half's addition)
+        int win, sub;
         if constexpr (GLV) {
           win = NWIN_MAIN - 1;
           sub = WB + 1;  // the second half's addition of the top window comes next
@@ -836,82 +920,25 @@ __global__ void __launch_bounds__(WG, (coz_occupancy<CU, GLV>())) k_scalarmul_co
           win = NWIN_MAIN - 2;
           sub = 0;
         }
-      }
-      bool fix_pending = false, fix_lane = false;
-      while (win >= WIN_END) {
-        const int nd = (S != 0 && win < 0) ? S : WB;
-        bool step_done;
-        if (fix_pending || sub < nd) {
-          UJac<CU> t;
-          if constexpr (UBS<CU>::DENSE) {
-            // P-256: the merged doubling, and the equal-points fix-up in a wave-uniform branch of its own.  Its
-            // selects are asm (u_cmov_ct), which the compiler does not hoist, so the common path is q = t (written
-            // with ?:, the branch is if-converted into 3 N v_cndmask that every doubling runs).
-            ujac_dbl_merged<CU>(t, q);
-            if (fix_pending) {
-              const uint64_t keep = ct_mask(!fix_lane);  // lanes without the fix-up keep q
-              u_cmov_ct(t.x, keep, q.x);
-              u_cmov_ct(t.y, keep, q.y);
-              u_cmov_ct(t.z, keep, q.z);
-              fix_pending = false;
-              fix_lane = false;
-            }
-            q = t;
+        bool fix_pending = false;
+        while (win >= WIN_END) {
+          const int nd = (S != 0 && win < 0) ? S : WB;
+          bool step_done;
+          if (fix_pending || sub < nd) {
+            dbl_step(fix_pending);
+            fix_pending = false;
+            step_done = true;
           } else {
-            ujac_dbl<CU>(t, q);
-            if (fix_pending) {
-              u_select(q.x, fix_lane, t.x, q.x);
-              u_select(q.y, fix_lane, t.y, q.y);
-              u_select(q.z, fix_lane, t.z, q.z);
-              fix_pending = false;
-              fix_lane = false;
+            fix_pending = add_step(win, GLV && sub == WB + 1);
+            step_done = !fix_pending;
+          }
+          if (step_done) {
+            if (sub < nd + (GLV ? 1 : 0)) {
+              ++sub;
             } else {
-              q = t;
+              sub = 0;
+              --win;
             }
-          }
-          step_done = true;
-        } else {
-          const bool second = GLV && sub == WB + 1;
-          uint32_t d;
-          bool neg;
-          booth(win, second, d, neg);
-          if (second && !LATTICE) neg = !neg;  // BLS12-381: [x^2]P = -sigma(P) = (beta x, -y)
-          T ex, ey;
-          if constexpr (GLV) {
-            T eb;
-            u3_load<CU>(ex, ey, eb, row(d ? d : 1));
-            if (second) ex = eb;
-          } else {
-            u2_load<CU>(ex, ey, row(d ? d : 1));
-          }
-          const bool q_inf = u_limbs_all_zero(q.z);
-          const bool e_skip = (d == 0);
-          UJac<CU> sum;
-          bool hz, rz;
-          ujac_madd_signed<CU>(sum, hz, rz, q, ex, ey, neg);
-          const bool same_x = hz && !q_inf && !e_skip;
-          fix_lane = same_x && rz;  // q == entry: needs a doubling
-          if (same_x && !rz) u_set_zero(sum.z);  // q == -entry
-          if (__builtin_amdgcn_ballot_w64(q_inf) != 0) {  // accumulator at infinity: the sum is the entry
-            U<CU, 2, 4> sy;
-            u_select(sy, neg, u_neg(ey), u_as<2, 4>(ey));
-            u_select(sum.x, q_inf, ex, sum.x);
-            u_select(sum.y, q_inf, u_reduce(sy), sum.y);
-            u_select(sum.z, q_inf, u_as<UJac<CU>::ZK, UJac<CU>::ZV>(one), sum.z);
-          }
-          const bool keep = e_skip || fix_lane;
-          u_select(q.x, keep, q.x, sum.x);
-          u_select(q.y, keep, q.y, sum.y);
-          u_select(q.z, keep, q.z, sum.z);
-          fix_pending = __builtin_amdgcn_ballot_w64(fix_lane) != 0;
-          step_done = !fix_pending;
-        }
-        if (step_done) {
-          if (sub < nd + (GLV ? 1 : 0)) {
-            ++sub;
-          } else {
-            sub = 0;
-            --win;
           }
         }
       }
