@@ -314,7 +314,8 @@ ECCX_DEV void ujac_madd_signed(UJac<CU>& r, bool& h_zero, bool& r_zero, const UJ
   } else if constexpr (UB<CU>::SPARSE) {
     r.y = u_mul_sub(rr, u_sub(v, x3), p.y, hhh);
   } else if constexpr (UBS<CU>::DENSE) {
-    r.y = u_mul_sub(rr, u_reduce(u_sub(v, x3)), p.y, hhh);  // P-256: tight operands, one reduction (K 1*1 per side)
+    // P-256: one reduction, v - x3 as a signed limb-wise difference (K 1*1 per side; V 3*3 + 3*2 < RP = 32)
+    r.y = u_mul_sub(rr, u_sdiff(v, x3), p.y, hhh);
   } else {
     auto y3a = u_mul(rr, u_sub(v, x3));
     auto y1h = u_mul(p.y, hhh);

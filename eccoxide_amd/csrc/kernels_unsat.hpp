@@ -164,16 +164,16 @@ ECCX_DEV void ujac_dbl(UJac<CU>& r, const UJac<CU>& p) {
 
 // 2P for the public-scalar ladder on P-256 (k_scalarmul_coz_unsat, CT = false): the a = -3 doubling above
 // with Y3 = alpha (4 beta - X3) - 2 (2 gamma)^2 in ONE reduction on signed columns (u_mul_sub_2sqr).  The
-// square's reduction and column extractions, the subtraction chain and the weak reduction of Y3 go; the
-// merged core takes one product of tight limbs per side, so 4 beta - X3 and 2 gamma are reduced instead.
-// 4 products + 3 squares + one merged product, 4 Montgomery reductions + 4 weak ones.
+// square's reduction and column extractions, the subtraction chain and the weak reduction of Y3 go.  The merged
+// core takes one product of tight limbs per side: 2 gamma comes tight out of the squarer (u_sqr2), and 4 beta - X3
+// enters as a signed limb-wise difference (u_sdiff), so neither costs a carry chain.
+// 4 products + 3 squares + one merged product, 4 Montgomery reductions + 2 weak ones (alpha, X3).
 template <class CU>
 ECCX_DEV void ujac_dbl_merged(UJac<CU>& r, const UJac<CU>& p) {
   static_assert(UBS<CU>::DENSE && !CU::Sat::A0, "written for a = -3 on p = -1 mod 2^B without the sparse form");
   auto delta = u_sqr(p.z);                          // (1,2)
-  auto gamma = u_sqr(p.y);                          // (1,2)
-  auto g2 = u_reduce(u_add(gamma, gamma));          // 2*gamma            (1,3)
-  auto g4 = u_add(g2, g2);                          // (2,6)
+  auto g2 = u_sqr2(p.y);                            // 2*gamma            (1,2)
+  auto g4 = u_add(g2, g2);                          // (2,4)
   auto b4 = u_mul(p.x, g4);                         // 4*beta             (1,2)
   auto t1 = u_sub(p.x, delta);                      // (3,7)
   auto t2 = u_add(p.x, delta);                      // (2,5)
@@ -182,7 +182,7 @@ ECCX_DEV void ujac_dbl_merged(UJac<CU>& r, const UJac<CU>& p) {
   auto x3 = u_reduce(u_sub(u_sub(u_sqr(alpha), b4), b4));  // alpha^2 - 8*beta  (1,3)
   auto yz = u_mul(p.y, p.z);                        // (1,2)
   r.x = x3;
-  r.y = u_mul_sub_2sqr(alpha, u_reduce(u_sub(b4, x3)), g2);  // K 1*1 and 2*1*1 <= KKS = 2; V 9 and 18 < RP = 32
+  r.y = u_mul_sub_2sqr(alpha, u_sdiff(b4, x3), g2);  // K 1*1 and 2*1*1 <= KKS = 2; V 3*3 + 2*2*2 < RP = 32
   r.z = u_fit<UJac<CU>::ZK, UJac<CU>::ZV>(u_add(yz, yz));  // 2*Y*Z      (2,4)
 }
 

@@ -255,10 +255,65 @@ struct UMacQC {
   }
 };
 
+// the queue of the signed columns for products whose second factor is signed (US): every term, and the pending
+// carry, goes in with v_mad_i64_i32
+template <int S>
+struct UMacQS {
+  uint32_t x[9], y[9], h;
+  int n = 0;
+  bool hc = false;
+  ECCX_DEV void push(uint64_t& acc, uint32_t a, int32_t b) {
+    x[n] = a;
+    y[n] = (uint32_t)b;
+    if (++n == 9) flush(acc);
+  }
+  ECCX_DEV void carry(uint64_t acc) {
+    h = (uint32_t)(acc >> 32);
+    hc = true;
+  }
+  ECCX_DEV void flush(uint64_t& acc) {
+    static_assert(S >= 1 && S <= 6, "carry factor 2^S must be an inline constant");
+    constexpr int F = 1 << S;
+#define ECCX_Q(i) x[i], y[i]
+    if (hc) {
+      switch (n) {
+        case 1: umad1_vis<F>(acc, h, ECCX_Q(0)); break;
+        case 2: umad2_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1)); break;
+        case 3: umad3_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2)); break;
+        case 4: umad4_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3)); break;
+        case 5: umad5_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4)); break;
+        case 6: umad6_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5)); break;
+        case 7: umad7_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6)); break;
+        case 8: umad8_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6), ECCX_Q(7)); break;
+        case 9: umad9_vis<F>(acc, h, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6), ECCX_Q(7), ECCX_Q(8)); break;
+        default: acc = (uint64_t)h << 32; scarry_hi<S>(acc); break;
+      }
+    } else {
+      switch (n) {
+        case 1: umad1_vi(acc, ECCX_Q(0)); break;
+        case 2: umad2_vi(acc, ECCX_Q(0), ECCX_Q(1)); break;
+        case 3: umad3_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2)); break;
+        case 4: umad4_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3)); break;
+        case 5: umad5_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4)); break;
+        case 6: umad6_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5)); break;
+        case 7: umad7_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6)); break;
+        case 8: umad8_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6), ECCX_Q(7)); break;
+        case 9: umad9_vi(acc, ECCX_Q(0), ECCX_Q(1), ECCX_Q(2), ECCX_Q(3), ECCX_Q(4), ECCX_Q(5), ECCX_Q(6), ECCX_Q(7), ECCX_Q(8)); break;
+        default: break;
+      }
+    }
+#undef ECCX_Q
+    n = 0;
+    hc = false;
+  }
+};
+
 // ---- product cores on raw limb arrays; bounds are checked by the typed wrappers -----------
 
 // Montgomery product / square (kinds 0 and 1): product scanning, one 64-bit column at a time
-template <class C, bool SQR, bool BCONST, bool LO32 = UB<C>::LO32>
+// DBL (with SQR): 2 a^2 from the same multiplies -- cross terms a2[i]*a2[j], diagonal a[i]*a2[i]; the columns carry
+// what a product with K1*K2 = 2 carries
+template <class C, bool SQR, bool BCONST, bool LO32 = UB<C>::LO32, bool DBL = false>
 ECCX_DEV void u_mul_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N]) {
   constexpr int N = C::N;
   constexpr bool PP1 = C::KIND == UK_MONT_PP1;
@@ -275,7 +330,11 @@ ECCX_DEV void u_mul_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], co
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; ++k) {
     const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
-    if constexpr (SQR) {
+    if constexpr (SQR && DBL) {
+#pragma unroll
+      for (int i = lo; 2 * i < k; ++i) qa.push(acc, a2[i], a2[k - i]);
+      if ((k & 1) == 0) qa.push(acc, a[k / 2], a2[k / 2]);
+    } else if constexpr (SQR) {
 #pragma unroll
       for (int i = lo; 2 * i < k; ++i) qa.push(acc, a[i], a2[k - i]);
       if ((k & 1) == 0) qa.push(acc, a[k / 2], a[k / 2]);
@@ -501,17 +560,24 @@ ECCX_DEV void u_mul_sub_core_mont(uint32_t (&r)[C::N], const uint32_t (&a)[C::N]
 // and the low word is taken as the Montgomery factor (-p^-1 mod 2^B = 1) exactly as in the unsigned core (32-bit
 // digits in columns 0..N-2, UB::LO32; the static_assert in UBS checks this budget).  With M < R (1 + 2^-26) the
 // result stays in (0, 3p): V1*V2 <= RP - 1 leaves (1 - 1/RP) p for the excess.
-template <class C, bool NEG_SQ>
-ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N],
+//
+// TB = int32_t: b is a signed operand (US: limb-wise difference of two tight values, |limb| < K * 2^B), and the
+// terms of a*b go in with v_mad_i64_i32.  Its negative terms join the negative side, which then holds at most
+// N (K1*K + K3*K4) products (or N (K1*K + 2 K3^2)): the typed wrappers keep that sum below 2^63 - 2^(64-B); the
+// positive side only loses terms.  The result is in (0, 3p) while V1*V + V3*V4 (2 V3^2) < RP.
+template <class C, bool NEG_SQ, class TB = uint32_t>
+ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const TB (&b)[C::N],
                                  const uint32_t (&c)[C::N], const uint32_t (&d)[C::N]) {
   constexpr int N = C::N;
+  constexpr bool BS = std::is_same_v<TB, int32_t>;
+  static_assert(BS || std::is_same_v<TB, uint32_t>, "second factor: unsigned limbs or signed differences");
   static_assert(C::KIND == UK_MONT_PP1 && C::SPARSE_N == 0, "p = -1 mod 2^B with p + 1 as plain digits");
   uint32_t m[N], t[N];
   int32_t nc[N];  // -c (NEG_SQ: -2c)
 #pragma unroll
   for (int i = 0; i < N; ++i) nc[i] = NEG_SQ ? -(int32_t)(c[i] << 1) : -(int32_t)c[i];
   uint64_t acc = 0;
-  UMacQC<false, 32 - C::B> qa;
+  std::conditional_t<BS, UMacQS<32 - C::B>, UMacQC<false, 32 - C::B>> qa;
   UMacQ<true> qm;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; ++k) {
@@ -536,7 +602,8 @@ ECCX_DEV void u_mul_sub_core_pp1(uint32_t (&r)[C::N], const uint32_t (&a)[C::N],
     if (k < N - 1) {
       // 32-bit digit as in u_mul_core_mont (UB::LO32); hi32(acc) is signed here
       m[k] = (uint32_t)acc;
-      qa.carry(acc, true);
+      if constexpr (BS) qa.carry(acc);
+      else qa.carry(acc, true);
       continue;
     }
     if (k < N) m[k] = (uint32_t)acc & C::MASK;
@@ -831,6 +898,71 @@ ECCX_DEV auto u_mul_sub_2sqr(const U<C, K1, V1>& a, const U<C, K2, V2>& b, const
   if constexpr (UB<C>::SPARSE) u_mul_sub_core_sparse<C, true>(r.v, a.v, b.v, c.v, c.v);
   else if constexpr (UBS<C>::DENSE) u_mul_sub_core_pp1<C, true>(r.v, a.v, b.v, c.v, c.v);
   else u_mul_sub_core_mont<C, true>(r.v, a.v, b.v, c.v, c.v);
+  return r;
+}
+
+// A signed operand for the merged products of the dense field (P-256): int32 limbs with |limb| < K * 2^B and
+// |value| < V * p.  Made by the limb-wise difference of two tight values -- no bias, no carry chain -- and taken
+// as the second factor of the first product, whose terms then go in with v_mad_i64_i32.
+template <class C, int K, int V>
+struct US {
+  static_assert(K >= 1 && UBS<C>::ks_ok(K), "signed limbs must stay below 2^31");
+  static_assert(V >= 1 && V <= 4096, "value bound out of range");
+  int32_t v[C::N];
+};
+
+// a - b limb by limb: both tight (each limb within 2^B), so every limb lies in (-2^B, 2^B) and the value in
+// (-V2 p, V1 p)
+template <class C, int V1, int V2>
+ECCX_DEV auto u_sdiff(const U<C, 1, V1>& a, const U<C, 1, V2>& b) {
+  US<C, 1, (V1 > V2 ? V1 : V2)> r;
+#pragma unroll
+  for (int i = 0; i < C::N; ++i) r.v[i] = (int32_t)(a.v[i] - b.v[i]);
+  return r;
+}
+
+// the negative side of a signed column with a signed first product: its negative terms and the subtracted product,
+// KK products' worth per term pair, and the carry in
+template <class C>
+constexpr bool ubs_neg_side_ok(int kk) {
+  return (uint64_t)C::N * (uint64_t)kk * UB<C>::COL <= (~(uint64_t)0 >> 1) - ((uint64_t)1 << (64 - C::B));
+}
+
+// a*b - c*d (+ p) with a signed b (dense field)
+template <class C, int K1, int V1, int K2, int V2, int K3, int V3, int K4, int V4>
+ECCX_DEV auto u_mul_sub(const U<C, K1, V1>& a, const US<C, K2, V2>& b, const U<C, K3, V3>& c, const U<C, K4, V4>& d) {
+  static_assert(UBS<C>::DENSE, "signed operands are implemented for p = -1 mod 2^B with p + 1 as plain digits");
+  static_assert(K1 * K2 <= UBS<C>::KKS && K3 * K4 <= UBS<C>::KKS, "a product overflows the signed columns");
+  static_assert(UBS<C>::ks_ok(K1) && UBS<C>::ks_ok(K3) && UBS<C>::ks_ok(K4), "negated / signed operands must stay below 2^31");
+  static_assert(ubs_neg_side_ok<C>(K1 * K2 + K3 * K4), "the negative side of a column overflows");
+  static_assert((uint32_t)(V1 * V2 + V3 * V4) < C::RP, "result outside (0, 3p)");
+  U<C, 1, 3> r;
+  u_mul_sub_core_pp1<C, false, int32_t>(r.v, a.v, b.v, c.v, d.v);
+  return r;
+}
+// a*b - 2*c^2 (+ p) with a signed b (dense field)
+template <class C, int K1, int V1, int K2, int V2, int K3, int V3>
+ECCX_DEV auto u_mul_sub_2sqr(const U<C, K1, V1>& a, const US<C, K2, V2>& b, const U<C, K3, V3>& c) {
+  static_assert(UBS<C>::DENSE, "signed operands are implemented for p = -1 mod 2^B with p + 1 as plain digits");
+  static_assert(K1 * K2 <= UBS<C>::KKS && 2 * K3 * K3 <= UBS<C>::KKS, "a product overflows the signed columns");
+  static_assert(UBS<C>::ks_ok(K1) && UBS<C>::ks_ok(2 * K3), "doubled / negated operands must stay below 2^31");
+  static_assert(ubs_neg_side_ok<C>(K1 * K2 + 2 * K3 * K3), "the negative side of a column overflows");
+  static_assert((uint32_t)(V1 * V2 + 2 * V3 * V3) < C::RP, "result outside (0, 3p)");
+  U<C, 1, 3> r;
+  u_mul_sub_core_pp1<C, true, int32_t>(r.v, a.v, b.v, c.v, c.v);
+  return r;
+}
+
+// 2 a^2 straight out of the squarer (dense field): the doubled limbs the square core holds anyway give the cross
+// terms a2[i]*a2[j] and the diagonal a[i]*a2[i] -- the same multiplies, a tight result, no carry chain
+template <class C, int V1>
+ECCX_DEV auto u_sqr2(const U<C, 1, V1>& a) {
+  static_assert(UBS<C>::DENSE && UB<C>::LO32, "written for p = -1 mod 2^B with p + 1 as plain digits");
+  static_assert(UB<C>::kk_ok(2, 1), "columns: a square with doubled terms carries a product with K1*K2 = 2");
+  static_assert(UB<C>::KMAX >= 2, "limbs: the doubled operand a << 1 (below 2 * 2^B) stays below 2^32");
+  static_assert(UB<C>::vout(2 * V1, V1) <= 3, "result too large: reduce the operand first");
+  U<C, 1, UB<C>::vout(2 * V1, V1)> r;
+  u_mul_core_mont<C, true, false, true, true>(r.v, a.v, a.v);
   return r;
 }
 
