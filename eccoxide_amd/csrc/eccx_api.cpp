@@ -183,6 +183,28 @@ Need need_var_fixup(const eccx_ctx* ctx, const CurveOps* ops, size_t n) {
   return {std::min(var_grid(ctx, ops, n), ctx->cus), ops->info.row_words};
 }
 
+// What the pairing needs for n units of `pairs` terms: the persistent grids of its two long kernels, the slab they
+// index by workgroup, and the [block][word][lane] rows of the units' Miller values and of the terms.  The entry points
+// and eccx_reserve both size from this.
+struct PairingNeed {
+  int miller_grid, finalexp_grid;
+  size_t slab_bytes, f_bytes, term_bytes;
+};
+PairingNeed need_pairing(const eccx_ctx* ctx, const CurveOps* ops, size_t n, size_t pairs) {
+  const size_t wg = eccx::LAUNCH_WG, row = (size_t)ops->pairing_row_words * wg * sizeof(uint32_t);
+  PairingNeed nd;
+  nd.miller_grid = ops->pairing_miller_grid(ctx->cus, n);
+  nd.finalexp_grid = ops->pairing_finalexp_grid(ctx->cus, n);
+  nd.slab_bytes = (size_t)std::max(nd.miller_grid, nd.finalexp_grid) * (size_t)ops->pairing_slab_words * wg * sizeof(uint32_t);
+  nd.f_bytes = (n + wg - 1) / wg * row;
+  nd.term_bytes = (n * pairs + wg - 1) / wg * row;
+  return nd;
+}
+int ensure_pairing(eccx_ctx* ctx, const PairingNeed& nd) {
+  const int rc = grow(ctx, B_SCRATCH, nd.slab_bytes);
+  return rc ? rc : grow(ctx, B_ROWS, nd.f_bytes + nd.term_bytes);
+}
+
 // result rows for n units
 int ensure_rows(eccx_ctx* ctx, const CurveOps* ops, size_t n) {
   return grow(ctx, B_ROWS, n * (size_t)ops->info.jac_words * sizeof(uint32_t));
@@ -870,6 +892,8 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     rc = ensure_slab<EdSignSlab>(ctx, B_EDSIGN, ops, max_n, nullptr);
   if (!rc && (what & ECCX_PREP_ECDSA_SIGN) && ops->ecdsa_sign_finish)
     rc = ensure_slab<EcdsaSignSlab>(ctx, B_ECSIGN, ops, max_n, nullptr);
+  // eccx_pairing / eccx_pairing_check: n * max(pairs, 1) <= max_n bounds the units, the terms and the grids by max_n's
+  if (!rc && (what & ECCX_PREP_PAIRING) && ops->pairing_miller) rc = ensure_pairing(ctx, need_pairing(ctx, ops, max_n, 1));
   // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
   // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
   return rc;
@@ -1447,6 +1471,75 @@ int eccx_hash_to_g2_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void*
 int eccx_hash_to_g2(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
                     uint8_t* out, uint8_t* flags, uint32_t opts) {
   return hash_to_curve_host(ctx, H2C_G2, n, msgs, offsets, dst, dst_len, out, flags, opts);
+}
+
+namespace {
+// eccx_pairing and eccx_pairing_check are one body: d_out == null compares with 1 on the device and leaves verdicts in
+// d_status, otherwise d_status takes the flags
+const char* const PAIRING_OPTS_MSG = "eccx_pairing: opts must be 0 or ECCX_VALIDATE_POINTS (nothing here is secret)";
+int pairing_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_g1, const void* d_g1_inf, const void* d_g2, const void* d_g2_inf,
+                void* d_out, bool want_value, void* d_status, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS) return arg_err(ctx, PAIRING_OPTS_MSG);
+  if (n == 0) return ECCX_OK;
+  if (pairs > 0xffffffffu || (pairs && n > (size_t)-1 / pairs / 192)) return arg_err(ctx, "eccx_pairing: n x pairs out of range");
+  if (int rc = begin_batch(ctx, d_status && (d_out || !want_value) && (pairs == 0 || (d_g1 && d_g2)))) return rc;
+  const CurveOps* ops = ops_of(ECCX_BLS12_381_G2);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const PairingNeed nd = need_pairing(ctx, ops, n, pairs);
+  if (int rc = ensure_pairing(ctx, nd)) return rc;
+  uint32_t* fbuf = ctx->rows();
+  uint32_t* terms = reinterpret_cast<uint32_t*>(ctx->buf[B_ROWS].p + nd.f_bytes);
+  uint8_t* status = static_cast<uint8_t*>(d_status);
+  HIP_TRY(ctx, ops->pairing_miller(nd.miller_grid, s, n, (uint32_t)pairs, static_cast<const uint8_t*>(d_g1),
+                                   static_cast<const uint8_t*>(d_g1_inf), static_cast<const uint8_t*>(d_g2),
+                                   static_cast<const uint8_t*>(d_g2_inf), terms, fbuf, status, ctx->scratch(), kopts_of(opts)));
+  HIP_TRY(ctx, ops->pairing_finalexp(nd.finalexp_grid, s, n, fbuf, want_value ? static_cast<uint8_t*>(d_out) : nullptr, status,
+                                     ctx->scratch()));
+  return ECCX_OK;
+}
+int pairing_host(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                 const uint8_t* g2_inf, uint8_t* out, bool want_value, uint8_t* status, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS) return arg_err(ctx, PAIRING_OPTS_MSG);
+  if (n == 0) return ECCX_OK;
+  if (pairs > 0xffffffffu || (pairs && n > (size_t)-1 / pairs / 192)) return arg_err(ctx, "eccx_pairing: n x pairs out of range");
+  if (!status || (want_value && !out) || (pairs && (!g1 || !g2))) return arg_err(ctx, "null buffer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // with pairs == 0 there is nothing to copy in: the input slots stay untouched
+  const bool in = pairs != 0;
+  HostBuf bufs[] = {in_buf(IO_K, in ? g1 : nullptr, pairs * 96),       in_buf(IO_P, in ? g2 : nullptr, pairs * 192),
+                    in_buf(IO_A, in ? g1_inf : nullptr, pairs),        in_buf(IO_B, in ? g2_inf : nullptr, pairs),
+                    out_buf(IO_O, want_value ? out : nullptr, 576),    out_buf(IO_F, status, 1)};
+  // one chunk: a chunk of units would be a batch of its own only in the unit-major buffers, and the kernels dwarf the copies
+  return host_pipeline(ctx, n, bufs, /*chunked=*/false, [&](size_t lo, size_t cnt, uint8_t* const* d) {
+    (void)lo;
+    return pairing_dev(ctx, cnt, pairs, d[0], d[2], d[1], d[3], d[4], want_value, d[5], opts, ctx->stream);
+  });
+}
+}  // namespace
+
+int eccx_pairing_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                     const void* d_g2_inf, void* d_out, void* d_flags, uint32_t opts, void* stream) {
+  return pairing_dev(ctx, n, pairs, d_g1, d_g1_inf, d_g2, d_g2_inf, d_out, true, d_flags, opts, stream);
+}
+int eccx_pairing(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                 const uint8_t* g2_inf, uint8_t* out, uint8_t* flags, uint32_t opts) {
+  return pairing_host(ctx, n, pairs, g1, g1_inf, g2, g2_inf, out, true, flags, opts);
+}
+int eccx_pairing_check_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                           const void* d_g2_inf, void* d_verdicts, uint32_t opts, void* stream) {
+  return pairing_dev(ctx, n, pairs, d_g1, d_g1_inf, d_g2, d_g2_inf, nullptr, false, d_verdicts, opts, stream);
+}
+int eccx_pairing_check(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                       const uint8_t* g2_inf, uint8_t* verdicts, uint32_t opts) {
+  return pairing_host(ctx, n, pairs, g1, g1_inf, g2, g2_inf, nullptr, false, verdicts, opts);
+}
+
+size_t eccx_pairing_lanes(const eccx_ctx* ctx) {
+  if (!ctx || hipSetDevice(ctx->device) != hipSuccess) return 0;
+  const PairingNeed nd = need_pairing(ctx, ops_of(ECCX_BLS12_381_G2), (size_t)-1 / 2, 0);
+  return (size_t)std::max(nd.miller_grid, nd.finalexp_grid) * eccx::LAUNCH_WG;
 }
 
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,

@@ -101,6 +101,7 @@ const CurveOps& ops_BLS12_381_G2() {
     t.base_ct = base_ct_;
     t.base_unsat = base_index_;
     h2c_ops_BLS12_381_G2(t);  // hashing to G2
+    pairing_ops_BLS12_381_G2(t);  // the pairing
     return t;
   }();
   return o;

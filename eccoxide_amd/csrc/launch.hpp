@@ -172,6 +172,19 @@ struct CurveOps {
   int (*h2c_map_grid)(int cus, size_t n);
   hipError_t (*h2c_clear)(int grid, hipStream_t s, size_t n, uint32_t* rows);
   int (*h2c_clear_grid)(int cus, size_t n);
+  // The pairing (kernels_pairing.hpp; bls12_381_g2 only, else null).  pairing_miller runs the shared loop of each unit's
+  // `pairs` terms (g1: n x pairs x 2 FB bytes, g2: n x pairs x 4 FB bytes, unit-major, with optional infinity flags) and
+  // leaves the unit's Miller value in fbuf and 0 / 2 (OPT_VALIDATE rejected a point) in status; pairing_finalexp turns
+  // fbuf into 576 bytes per unit (out != null) or, with out == null, status into the verdict 0 / 1 / 2.  Buffers in
+  // [block][word][lane] order: fbuf ceil(n / WG) rows and terms pairs x ceil(n / WG) rows of pairing_row_words x WG
+  // words; slab: pairing_slab_words x WG words per workgroup of the larger grid.
+  hipError_t (*pairing_miller)(int grid, hipStream_t s, size_t n, uint32_t pairs, const uint8_t* g1, const uint8_t* g1_inf,
+                               const uint8_t* g2, const uint8_t* g2_inf, uint32_t* terms, uint32_t* fbuf, uint8_t* status,
+                               uint32_t* slab, uint32_t opts);
+  hipError_t (*pairing_finalexp)(int grid, hipStream_t s, size_t n, uint32_t* fbuf, uint8_t* out, uint8_t* status, uint32_t* slab);
+  int (*pairing_miller_grid)(int cus, size_t n);
+  int (*pairing_finalexp_grid)(int cus, size_t n);
+  int pairing_row_words, pairing_slab_words;
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
@@ -194,6 +207,7 @@ const CurveOps& ops_ED25519();
 const CurveOps& ops_P256K1();
 const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring slots (var, base, point_add are null)
 void h2c_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_h2c.hip: the h2c_* slots of ops_BLS12_381_G2
+void pairing_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_pairing.hip: the pairing_* slots of ops_BLS12_381_G2
 
 // curve25519 x-only ladder (k_ed25519.hip): rows of row_words<8>() = 24 words per unit
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u,

@@ -35,6 +35,8 @@ PREP_ED25519 = 256
 PREP_ED25519_SIGN = 512
 PREP_ECDSA_SIGN = 1024
 PREP_H2C = 2048
+PREP_PAIRING = 4096
+PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
 SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
@@ -149,18 +151,20 @@ class Engine:
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
-                h2c: bool = False):
+                h2c: bool = False, pairing: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
         row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key; h2c: the row buffer
-        hash_to_g1 works in (curve "bls12_381_g1") or hash_to_g2 (curve "bls12_381_g2": two rows per unit)."""
+        hash_to_g1 works in (curve "bls12_381_g1") or hash_to_g2 (curve "bls12_381_g2": two rows per unit); pairing: the
+        slab and rows of pairing / pairing_check (curve "bls12_381_g2") for every shape with n * max(pairs, 1) <= max_n."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
                                            | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)
                                            | (PREP_ED25519_SIGN if ed25519_sign else 0)
-                                           | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)))
+                                           | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)
+                                           | (PREP_PAIRING if pairing else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -445,6 +449,93 @@ class Engine:
         """Hash a batch of messages to BLS12-381 G2 (eccx_hash_to_g2; RFC 9380, g2::Point::hash_to_curve), as hash_to_g1.
         Returns (points n x 192 affine x || y, each coordinate c1 || c0, flags n)."""
         return self._hash_to(self._lib.eccx_hash_to_g2, 192, messages, dst, nonuniform)
+
+    def pairing(self, g1: bytes, g2: bytes, pairs: int = 1, *, g1_inf: Optional[bytes] = None, g2_inf: Optional[bytes] = None,
+                validate: bool = False, n: Optional[int] = None):
+        """The product of `pairs` BLS12-381 pairings per unit (eccx_pairing; pairing, multi_miller_loop(..)
+        .final_exponentiation()): g1 is n x pairs x 96 bytes, g2 n x pairs x 192, unit-major; the optional flag arrays are
+        n x pairs bytes, a flagged term contributes 1.  n is needed only with pairs == 0.  Returns (values n x 576, flags n)."""
+        n = self._pairing_units(len(g1), len(g2), pairs, g1_inf, g2_inf, n)
+        out = ctypes.create_string_buffer(max(1, 576 * n))
+        flags = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_pairing(self._ctx, n, pairs, g1 if pairs else None, g1_inf, g2 if pairs else None, g2_inf, out,
+                                           flags, VALIDATE_POINTS if validate else 0))
+        return out.raw[:576 * n], flags.raw[:n]
+
+    def pairing_check(self, g1: bytes, g2: bytes, pairs: int = 2, *, g1_inf: Optional[bytes] = None,
+                      g2_inf: Optional[bytes] = None, validate: bool = False, n: Optional[int] = None) -> bytes:
+        """Whether each unit's product of pairings is 1, compared on the device (eccx_pairing_check): n verdict bytes,
+        PAIRING_NOT_ONE / PAIRING_ONE / PAIRING_REJECTED.  Arguments as pairing."""
+        n = self._pairing_units(len(g1), len(g2), pairs, g1_inf, g2_inf, n)
+        verdicts = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_pairing_check(self._ctx, n, pairs, g1 if pairs else None, g1_inf, g2 if pairs else None, g2_inf,
+                                                 verdicts, VALIDATE_POINTS if validate else 0))
+        return verdicts.raw[:n]
+
+    @staticmethod
+    def _pairing_units(g1_len, g2_len, pairs, g1_inf, g2_inf, n):
+        if pairs < 0:
+            raise ValueError("pairs must not be negative")
+        if pairs == 0:
+            if n is None:
+                raise ValueError("pairs == 0: pass n")
+            return int(n)
+        if g1_len % (96 * pairs) or g2_len != g1_len * 2:
+            raise ValueError(f"g1 must be n x {pairs} x 96 bytes and g2 n x {pairs} x 192")
+        units = g1_len // (96 * pairs)
+        if n is not None and n != units:
+            raise ValueError(f"n = {n}, but the buffers hold {units} units")
+        for name, f in (("g1_inf", g1_inf), ("g2_inf", g2_inf)):
+            if f is not None and len(f) != units * pairs:
+                raise ValueError(f"{name}: expected {units * pairs} flag bytes, got {len(f)}")
+        return units
+
+    def pairing_lanes(self) -> int:
+        """Lanes of the pairing's largest persistent launch: larger batches take the grid-stride path."""
+        return int(self._lib.eccx_pairing_lanes(self._ctx))
+
+    def pairing_t(self, g1, g2, pairs: int = 1, out=None, flags=None, *, g1_inf=None, g2_inf=None, validate: bool = False,
+                  n: Optional[int] = None, stream: Optional[int] = None):
+        """Device-tensor form of pairing (eccx_pairing_dev): g1, g2 and the optional flag tensors are what scalarmul_*_t,
+        hash_to_g2_t and point_decompress_t return.  Enqueued on `stream` (default: torch's current stream); returns
+        (values n x 576, flags n) tensors."""
+        return self._pairing_t(True, g1, g2, pairs, out, flags, g1_inf, g2_inf, validate, n, stream)
+
+    def pairing_check_t(self, g1, g2, pairs: int = 2, verdicts=None, *, g1_inf=None, g2_inf=None, validate: bool = False,
+                        n: Optional[int] = None, stream: Optional[int] = None):
+        """Device-tensor form of pairing_check (eccx_pairing_check_dev); returns the n verdict bytes as a tensor."""
+        return self._pairing_t(False, g1, g2, pairs, None, verdicts, g1_inf, g2_inf, validate, n, stream)[1]
+
+    def _pairing_t(self, want_value, g1, g2, pairs, out, status, g1_inf, g2_inf, validate, n, stream):
+        import torch
+
+        if pairs < 0:
+            raise ValueError("pairs must not be negative")
+        if pairs:
+            units = self._units(g1, 96 * pairs, "g1")
+            if n is not None and n != units:
+                raise ValueError(f"n = {n}, but g1 holds {units} units")
+            n = units
+            self._tensors(n * pairs, ("g1", g1, 96), ("g2", g2, 192), ("g1_inf", g1_inf, 1), ("g2_inf", g2_inf, 1))
+        elif n is None:
+            raise ValueError("pairs == 0: pass n")
+        dev = torch.device("cuda", self.device)
+        if want_value and out is None:
+            out = torch.empty((n, 576), dtype=torch.uint8, device=dev)
+        if status is None:
+            status = torch.empty((n,), dtype=torch.uint8, device=dev)
+        self._tensors(n, ("out", out, 576), ("flags", status, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: t.data_ptr() if (t is not None and pairs) else None
+        opts = VALIDATE_POINTS if validate else 0
+        if want_value:
+            self._check(self._lib.eccx_pairing_dev(self._ctx, n, pairs, ptr(g1), ptr(g1_inf), ptr(g2), ptr(g2_inf), out.data_ptr(),
+                                                   status.data_ptr(), opts, stream))
+        else:
+            self._check(self._lib.eccx_pairing_check_dev(self._ctx, n, pairs, ptr(g1), ptr(g1_inf), ptr(g2), ptr(g2_inf),
+                                                         status.data_ptr(), opts, stream))
+        return out, status
 
     def _hash_to(self, fn, width, messages, dst, nonuniform):
         import numpy as np

@@ -30,6 +30,8 @@
  *   eccx_hash_to_g2[_dev]        g2::Point::hash_to_curve / encode_to_curve   src/curve/bls12_381/g2.rs:218-238
  *                              -> hash_to_field_g2, map_to_curve_g2, the any-field sqrt_ratio   hash_to_curve.rs:255-305,
  *                              :501-529; clear_cofactor g2.rs:161-171
+ *   eccx_pairing[_dev], eccx_pairing_check[_dev]  pairing, multi_miller_loop(..).final_exponentiation()
+ *                              src/curve/bls12_381/pairing.rs:166-197, 263-272, 334, 360, 616-626
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
@@ -92,6 +94,8 @@
  * follows its message length, and the additions behind the map take wave-uniform branches on Q0 = +-Q1.
  * eccx_hash_to_g2 likewise: public messages, no secret-data promise.  Its map resolves its cases by selects and its
  * additions are the complete formulas, so what follows the data is the SHA-256 block count of a lane alone.
+ * eccx_pairing and eccx_pairing_check: nothing is secret -- points, signatures and messages are public -- so there is no
+ * ECCX_CT_SCAN form and no promise about branches; a term with an infinity flag is skipped by a per-lane predicate.
  *
  * MEMORY AND BLOCKING.  A context is bound to one GPU and owns
  *   - the window-table slab of the variable-base ladders: resident lanes x 17 rows (P-256:
@@ -233,6 +237,9 @@ enum {
                                    slab); with ECCX_PREP_HOST the copies of the host form's points and flags -- its message
                                    slot grows on demand, as Ed25519's does.  bls12_381_g2: the same for eccx_hash_to_g2,
                                    whose cofactor chain takes a second row per unit (2 x 336 bytes) */
+  ECCX_PREP_PAIRING = 1u << 12, /* eccx_reserve (bls12_381_g2): the slab and the rows of eccx_pairing / eccx_pairing_check for
+                                   every shape with n * max(pairs, 1) <= max_n: 4 KB per resident lane, and 672 bytes per
+                                   unit and per term */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -252,6 +259,13 @@ enum {
                              decrease */
   ECCX_SIG_BAD_KEY = 3    /* ECDSA: the public key is non-canonical, off the curve or the identity, or its SEC1 bytes do
                              not decode.  Ed25519: A fails decode_point (small and mixed order keys are legal) */
+};
+
+/* eccx_pairing_check: one verdict byte per unit */
+enum {
+  ECCX_PAIRING_NOT_ONE = 0,
+  ECCX_PAIRING_ONE = 1,     /* the product of the unit's pairings is 1 (the empty product included) */
+  ECCX_PAIRING_REJECTED = 2 /* ECCX_VALIDATE_POINTS refused one of the unit's finite points */
 };
 
 /* eccx_ecdsa_sign / eccx_ecdsa_public_key: one status byte per unit */
@@ -491,6 +505,44 @@ int eccx_hash_to_g2(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t
                     uint8_t* out, uint8_t* flags, uint32_t opts);
 int eccx_hash_to_g2_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
                         void* d_out, void* d_flags, uint32_t opts, void* stream);
+
+/* The BLS12-381 optimal-ate pairing, batched: unit i is the product over j < pairs of e(P_ij, Q_ij)
+ * (pairing, multi_miller_loop(..).final_exponentiation(): src/curve/bls12_381/pairing.rs:166-197, 263-272, 334, 360), the
+ * value the reference computes -- not its cube, which the common (x - 1)^2 chains give.  eccx_pairing_check compares the
+ * product with 1 on the device (pairing.rs:616-626): what BLS verification (e(pk, H(m)) e(-G1, sig) = 1), aggregate
+ * verification and KZG openings reduce to.  A unit's terms share one Miller loop (one Fp12 squaring per bit for the whole
+ * product) and one final exponentiation.
+ *   g1      : n x pairs x 96, unit-major (unit i's terms are contiguous): the affine x || y record eccx_scalarmul_*,
+ *             eccx_hash_to_g1 and eccx_point_decompress write for ECCX_BLS12_381_G1
+ *   g2      : n x pairs x 192: the ECCX_BLS12_381_G2 record, each coordinate c1 || c0
+ *   g1_inf, g2_inf : n x pairs flag bytes as those entry points write them, or NULL (every point is finite).  A term
+ *             with a non-zero flag on either side contributes 1, whatever its coordinate bytes are.
+ *   pairs   : 0 is legal and gives the empty product (value 1, verdict ECCX_PAIRING_ONE); g1, g2 may then be NULL
+ *   out     : n x 576: the twelve Fp coefficients as 48-byte big-endian canonical integers from the highest tower
+ *             coefficient down -- Fp12 c1 || c0, each Fp6 c2 || c1 || c0, each Fp2 c1 || c0, which extends the c1 || c0
+ *             rule of the Fp2 records.  The reference has no byte form for Fp12; this one is the library's own.
+ *   flags   : n bytes: 0 for a value, ECCX_FLAG_REJECTED with zero bytes where a point was rejected
+ *   verdicts: n bytes, ECCX_PAIRING_*
+ *   opts    : 0 or ECCX_VALIDATE_POINTS; anything else is ECCX_ERR_ARG.  With ECCX_VALIDATE_POINTS a finite point with a
+ *             coordinate >= p or off its curve rejects its unit, and only that unit.  Without it the caller guarantees
+ *             canonical points of G1 and G2; other input gives an unspecified value or verdict, never an out-of-bounds
+ *             access.  SUBGROUP MEMBERSHIP IS NOT TESTED HERE: it is the decoder's job -- eccx_point_decompress with
+ *             ECCX_CHECK_SUBGROUP writes exactly these records.
+ * n == 0 returns ECCX_OK whatever the pointers are; a null buffer otherwise is ECCX_ERR_ARG ("null buffer").  The _dev forms
+ * enqueue on `stream` without synchronising; after eccx_reserve(ctx, ECCX_BLS12_381_G2, max_n, ECCX_PREP_PAIRING) a _dev call
+ * with n * max(pairs, 1) <= max_n neither allocates, frees nor synchronises.  The Miller value before the final
+ * exponentiation is not exposed: its bytes depend on the scaling of the lines, which the implementation is free to choose. */
+int eccx_pairing(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                 const uint8_t* g2_inf, uint8_t* out, uint8_t* flags, uint32_t opts);
+int eccx_pairing_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                     const void* d_g2_inf, void* d_out, void* d_flags, uint32_t opts, void* stream);
+int eccx_pairing_check(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                       const uint8_t* g2_inf, uint8_t* verdicts, uint32_t opts);
+int eccx_pairing_check_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                           const void* d_g2_inf, void* d_verdicts, uint32_t opts, void* stream);
+/* The lanes of the pairing's largest persistent launch on this context's GPU (resident workgroups x 256): a batch of more
+ * units takes the kernels' grid-stride path.  0 for a null context. */
+size_t eccx_pairing_lanes(const eccx_ctx* ctx);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

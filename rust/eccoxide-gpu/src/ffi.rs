@@ -60,6 +60,7 @@ pub const ECCX_PREP_ED25519: u32 = 1 << 8; // eccx_ed25519_verify's working slab
 pub const ECCX_PREP_ED25519_SIGN: u32 = 1 << 9; // eccx_ed25519_sign's working slab, rows for 2 * max_n lanes
 pub const ECCX_PREP_ECDSA_SIGN: u32 = 1 << 10; // eccx_ecdsa_sign's / eccx_ecdsa_public_key's working slab
 pub const ECCX_PREP_H2C: u32 = 1 << 11; // eccx_hash_to_g1's / eccx_hash_to_g2's result rows
+pub const ECCX_PREP_PAIRING: u32 = 1 << 12; // eccx_pairing's / eccx_pairing_check's slab and rows
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -71,6 +72,11 @@ pub const ECCX_SIG_INVALID: u8 = 0;
 pub const ECCX_SIG_VALID: u8 = 1;
 pub const ECCX_SIG_MALFORMED: u8 = 2;
 pub const ECCX_SIG_BAD_KEY: u8 = 3;
+
+// verdicts of eccx_pairing_check, one byte per unit
+pub const ECCX_PAIRING_NOT_ONE: u8 = 0;
+pub const ECCX_PAIRING_ONE: u8 = 1;
+pub const ECCX_PAIRING_REJECTED: u8 = 2;
 
 // status bytes, one per unit (eccx_ecdsa_sign, eccx_ecdsa_public_key)
 pub const ECCX_SIGN_NONE: u8 = 0;
@@ -160,6 +166,19 @@ extern "C" {
                            out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
     pub fn eccx_hash_to_g2_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8,
                                dst_len: usize, d_out: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+
+    // products of pairings, batched                         pairing, multi_miller_loop(..).final_exponentiation()
+    pub fn eccx_pairing(ctx: *mut eccx_ctx, n: usize, pairs: usize, g1: *const u8, g1_inf: *const u8, g2: *const u8,
+                        g2_inf: *const u8, out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_pairing_dev(ctx: *mut eccx_ctx, n: usize, pairs: usize, d_g1: *const c_void, d_g1_inf: *const c_void,
+                            d_g2: *const c_void, d_g2_inf: *const c_void, d_out: *mut c_void, d_flags: *mut c_void, opts: u32,
+                            stream: *mut c_void) -> c_int;
+    pub fn eccx_pairing_check(ctx: *mut eccx_ctx, n: usize, pairs: usize, g1: *const u8, g1_inf: *const u8, g2: *const u8,
+                              g2_inf: *const u8, verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_pairing_check_dev(ctx: *mut eccx_ctx, n: usize, pairs: usize, d_g1: *const c_void, d_g1_inf: *const c_void,
+                                  d_g2: *const c_void, d_g2_inf: *const c_void, d_verdicts: *mut c_void, opts: u32,
+                                  stream: *mut c_void) -> c_int;
+    pub fn eccx_pairing_lanes(ctx: *const eccx_ctx) -> usize;
 
     // X25519 over a batch                                    protocol::x25519::x25519
     pub fn eccx_x25519(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,

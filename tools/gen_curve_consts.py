@@ -538,6 +538,55 @@ def emit_bls_g2_h2c(out):
     out.append("};")
 
 
+def emit_bls_pairing(out):
+    """BLS12_381_PAIRING: what the tower above Fp2 and the final exponentiation need (ufe12.hpp, kernels_pairing.hpp), in
+    the working form of BLS12_381U, all derived here from p, the seed and xi = 1 + u.  Fp12 is held in the basis 1, w, ..,
+    w^5 over Fp2 (w^6 = xi), so the Frobenius multiplies the conjugated coefficient of w^k by gamma^k with
+    gamma = xi^((p - 1) / 6); the Fp6 coefficients xi^((p - 1) / 3) and xi^(2 (p - 1) / 3) are gamma^2 and gamma^4.
+    LAMBDA3 = (x - 1)^2 / 3, the one long exponent of the hard part (p^4 - p^2 + 1) / r = lambda3 (p + x)(p^2 + x^2 - 1) + 1."""
+    p = CURVES[3][1]
+    r = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+    x_abs = 0xD201000000010000
+
+    def mul(a, b):
+        return ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)
+
+    def power(a, e):
+        acc = (1, 0)
+        while e:
+            if e & 1:
+                acc = mul(acc, a)
+            a = mul(a, a)
+            e >>= 1
+        return acc
+
+    xi = (1, 1)
+    assert (p - 1) % 6 == 0
+    gamma = power(xi, (p - 1) // 6)
+    g = [(1, 0)]
+    for _ in range(5):
+        g.append(mul(g[-1], gamma))
+    assert mul(g[5], gamma) == power(xi, p - 1)           # gamma^6 = xi^(p-1)
+    assert g[2] == power(xi, (p - 1) // 3) and g[4] == power(xi, 2 * (p - 1) // 3)
+    assert power(xi, (p * p - 1) // 2) != (1, 0)          # w^2 = v, v^3 = xi defines a field: xi is no square ...
+    assert power(xi, (p * p - 1) // 3) != (1, 0)          # ... and no cube in Fp2
+    lam3, rem = divmod((x_abs + 1) ** 2, 3)               # x = -x_abs
+    assert rem == 0
+    assert (p ** 4 - p ** 2 + 1) % r == 0
+    assert lam3 * (p - x_abs) * (p * p + x_abs * x_abs - 1) + 1 == (p ** 4 - p ** 2 + 1) // r
+    bits, n = 28, 14
+    R = 1 << (bits * n)
+    mont = lambda v: digits(v * R % p, bits, n)
+    out.append("")
+    out.append("struct BLS12_381_PAIRING {  // the tower above Fp2 and the final exponentiation, working form of BLS12_381U")
+    out.append(arr2("GAMMA0", [mont(g[k][0]) for k in range(6)]) + "  // row k: gamma^k = xi^(k (p-1) / 6), real parts")
+    out.append(arr2("GAMMA1", [mont(g[k][1]) for k in range(6)]) + "  // ... imaginary parts; rows 2, 4: the Fp6 coefficients")
+    nw = (lam3.bit_length() + 31) // 32
+    out.append("  static constexpr int LAMBDA3_BITS = %d;  // of (x - 1)^2 / 3" % lam3.bit_length())
+    out.append("  static constexpr uint32_t LAMBDA3[%d] = {%s};" % (nw, ", ".join("0x%08xu" % ((lam3 >> (32 * i)) & 0xFFFFFFFF) for i in range(nw))))
+    out.append("};")
+
+
 def main():
     out = ["// @generated by tools/gen_curve_consts.py -- do not edit.",
            "// Montgomery constants, 32-bit little-endian limbs, R = 2^(32*L).", ""]
@@ -621,6 +670,7 @@ def main():
     emit_bls_h2c(out)
     emit_bls_g2(out)
     emit_bls_g2_h2c(out)
+    emit_bls_pairing(out)
     sys.stdout.write("\n".join(out) + "\n")
 
 
