@@ -1545,6 +1545,7 @@ size_t eccx_pairing_lanes(const eccx_ctx* ctx) {
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,
                     uint32_t opts, void* stream) {
   if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_X25519_RAW_LADDER) return arg_err(ctx, "eccx_x25519: opts must be 0 or ECCX_X25519_RAW_LADDER");
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_scalars && d_out && d_flags)) return rc;
   const CurveOps* ops = ops_of(ECCX_ED25519);
@@ -1562,6 +1563,7 @@ int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* 
 int eccx_x25519(eccx_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* u, uint8_t* out, uint8_t* flags,
                 uint32_t opts) {
   if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_X25519_RAW_LADDER) return arg_err(ctx, "eccx_x25519: opts must be 0 or ECCX_X25519_RAW_LADDER");
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, scalars && out && flags)) return rc;
   HostBuf bufs[] = {in_buf(IO_K, scalars, 32), in_buf(IO_P, u, 32), out_buf(IO_O, out, 32), out_buf(IO_F, flags, 1)};

@@ -555,7 +555,8 @@ size_t eccx_pairing_lanes(const eccx_ctx* ctx);
  *          (x25519_base, x25519.rs:49-51)
  *   out  : n x 32 little-endian u-coordinates of the results
  *   flags: 1 where the result is zero (point at infinity / low-order input: callers doing
- *          Diffie-Hellman must reject it, x25519.rs:33-35), else 0 */
+ *          Diffie-Hellman must reject it, x25519.rs:33-35), else 0
+ * Any option bit other than ECCX_X25519_RAW_LADDER is refused with ECCX_ERR_ARG. */
 int eccx_x25519(eccx_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* u, uint8_t* out, uint8_t* flags,
                 uint32_t opts);
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,
