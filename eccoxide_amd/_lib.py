@@ -40,6 +40,8 @@ SYMBOLS = {
     "eccx_point_compress_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_double_scalarmul_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_x25519_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_x448": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_x448_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_ecdsa_verify": (c_int, [c_void_p, c_int, c_size_t, _u8p, c_size_t, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_ecdsa_verify_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_ecdsa_sign": (c_int, [c_void_p, c_int, c_size_t, _u8p, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),

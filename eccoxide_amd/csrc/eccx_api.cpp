@@ -209,6 +209,11 @@ int ensure_pairing(eccx_ctx* ctx, const PairingNeed& nd) {
 int ensure_rows(eccx_ctx* ctx, const CurveOps* ops, size_t n) {
   return grow(ctx, B_ROWS, n * (size_t)ops->info.jac_words * sizeof(uint32_t));
 }
+// result rows of eccx_x448 (k_curve448.hip): (X2, X2, Z2) as 16 digits each
+constexpr size_t X448_BYTES = 56;
+int ensure_x448_rows(eccx_ctx* ctx, size_t n) {
+  return grow(ctx, B_ROWS, n * (size_t)eccx::x448_row_words() * sizeof(uint32_t));
+}
 // the slab for every ladder of a launch path, and result rows for `rows` units
 int ensure_work(eccx_ctx* ctx, const CurveOps* ops, size_t rows, std::initializer_list<Need> needs) {
   size_t bytes = 0;
@@ -878,11 +883,18 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
                         ct && !ops->info.edwards ? need_var_fixup(ctx, ops, max_n) : none,
                         mirror ? need_var_mirror(ctx, ops, max_n) : none});
   if (rc) return rc;
+  // eccx_x448 has no curve of its own: its rows, and its host form's four slots, are sized beside whatever the id asks for
+  if (what & ECCX_PREP_X448) rc = ensure_x448_rows(ctx, max_n);
+  if (rc) return rc;
   if (what & ECCX_PREP_HOST) {  // device-side copies of the host-buffer entry points' arguments
     const size_t pb = 2 * (size_t)ops->info.fb, sb = (size_t)ops->info.sb;
     // IO_K: scalars, or the first operand of the group law; IO_J: the second scalar of the verify shape
     const size_t per_unit[NIO] = {std::max(pb, sb), pb, pb, 1, sb, 1, 1};
     for (int slot = 0; slot < NIO && !rc; ++slot) rc = grow(ctx, B_IO + slot, max_n * per_unit[slot]);
+    if (what & ECCX_PREP_X448) {
+      const size_t x448_unit[4] = {X448_BYTES, X448_BYTES, X448_BYTES, 1};  // IO_K, IO_P, IO_O, IO_F
+      for (int slot = 0; slot < 4 && !rc; ++slot) rc = grow(ctx, B_IO + slot, max_n * x448_unit[slot]);
+    }
     if (rc) return rc;
   }
   // the working slabs of eccx_ecdsa_verify, eccx_ed25519_verify, eccx_ed25519_sign and eccx_ecdsa_sign / _public_key
@@ -1569,6 +1581,36 @@ int eccx_x25519(eccx_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* 
   HostBuf bufs[] = {in_buf(IO_K, scalars, 32), in_buf(IO_P, u, 32), out_buf(IO_O, out, 32), out_buf(IO_F, flags, 1)};
   return host_pipeline(ctx, n, bufs, /*chunked=*/true, [&](size_t, size_t cnt, uint8_t* const* d) {
     return eccx_x25519_dev(ctx, cnt, d[0], d[1], d[2], d[3], opts, ctx->stream);
+  });
+}
+
+int eccx_x448_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,
+                  uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_X448_RAW_LADDER) return arg_err(ctx, "eccx_x448: opts must be 0 or ECCX_X448_RAW_LADDER");
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_scalars && d_out && d_flags)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t* flags = static_cast<uint8_t*>(d_flags);
+  if (int rc = ensure_x448_rows(ctx, n)) return rc;
+  const uint32_t kopts = (opts & ECCX_X448_RAW_LADDER) ? 0u : (1u << 4);  // OPT_X448_RFC
+  HIP_TRY(ctx, eccx::launch_x448_ladder(eccx::x448_ladder_grid(ctx->cus, n), s, n, static_cast<const uint8_t*>(d_scalars),
+                                        static_cast<const uint8_t*>(d_u), ctx->rows(), flags, kopts));
+  const size_t per_lane = (size_t)eccx::x448_norm_units();
+  HIP_TRY(ctx, eccx::launch_x448_to_u(grid(ctx, (n + per_lane - 1) / per_lane, 4), s, n, ctx->rows(), static_cast<uint8_t*>(d_out),
+                                      flags));
+  return ECCX_OK;
+}
+
+int eccx_x448(eccx_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* u, uint8_t* out, uint8_t* flags, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_X448_RAW_LADDER) return arg_err(ctx, "eccx_x448: opts must be 0 or ECCX_X448_RAW_LADDER");
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, scalars && out && flags)) return rc;
+  HostBuf bufs[] = {in_buf(IO_K, scalars, X448_BYTES), in_buf(IO_P, u, X448_BYTES), out_buf(IO_O, out, X448_BYTES),
+                    out_buf(IO_F, flags, 1)};
+  return host_pipeline(ctx, n, bufs, /*chunked=*/true, [&](size_t, size_t cnt, uint8_t* const* d) {
+    return eccx_x448_dev(ctx, cnt, d[0], d[1], d[2], d[3], opts, ctx->stream);
   });
 }
 

@@ -214,6 +214,15 @@ hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t
                                 uint32_t* rows, uint8_t* flags, uint32_t opts);
 hipError_t launch_x25519_to_u(int grid, hipStream_t s, size_t n, const uint32_t* rows, uint8_t* out, uint8_t* flags);
 
+// curve448 x-only ladder (k_curve448.hip): rows of x448_row_words() = 48 words per unit, normalised x448_norm_units()
+// units per lane; the ladder's persistent grid follows its residency (registers: two waves per SIMD)
+hipError_t launch_x448_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u, uint32_t* rows,
+                              uint8_t* flags, uint32_t opts);
+hipError_t launch_x448_to_u(int grid, hipStream_t s, size_t n, const uint32_t* rows, uint8_t* out, uint8_t* flags);
+int x448_ladder_grid(int cus, size_t n);
+int x448_row_words();
+int x448_norm_units();
+
 constexpr int LAUNCH_WG = 256;
 
 template <class K>

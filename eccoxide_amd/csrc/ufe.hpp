@@ -7,7 +7,7 @@
 // is ONE v_mad_u64_u32, squares really cost half the cross products, additions are N
 // independent v_add_u32 and there is no conditional subtraction.
 //
-// Four kinds of field (C::KIND), all reproducing the reference's values modulo p only
+// Five kinds of field (C::KIND), all reproducing the reference's values modulo p only
 // (canonical bytes are produced at the very end, u_to_canonical):
 //   0  Montgomery, R = 2^(B*N), p = -1 mod 2^B: the Montgomery factor m is the low limb of
 //      the accumulator itself and "+ m*p" becomes "drop that limb, + m*(p+1)"; p + 1 has few
@@ -20,6 +20,10 @@
 //   3  p = 2^255 - 19, plain representation, 9 x 29 = 261 bits: the upper columns are carried
 //      into digits first and enter the lower columns times 2^261 mod p = 1216
 //                                                          (src/curve/fiat/curve25519_64.rs)
+//   4  p = 2^448 - 2^224 - 1 ("Goldilocks"), plain representation, 16 x 28 = 448 bits exactly: the upper columns are
+//      carried into digits h first, as for kind 3; phi = 2^224 is the boundary of limb 8 and 2^448 = phi + 1, so digit
+//      h_j enters the lower columns j and j + 8 -- for j >= 8, where j + 8 wraps once more, columns j - 8 and (twice) j
+//                                                                                   (src/curve/curve448.rs)
 //
 // The price is bookkeeping, done at compile time.  Every value carries two bounds in its
 // type, U<C, K, V>:
@@ -89,7 +93,30 @@ __device__ __forceinline__ void scarry_hi(uint64_t& acc) {
   acc = r;
 }
 
-enum : int { UK_MONT_PP1 = 0, UK_MONT = 1, UK_MERSENNE = 2, UK_PM19 = 3 };
+enum : int { UK_MONT_PP1 = 0, UK_MONT = 1, UK_MERSENNE = 2, UK_PM19 = 3, UK_GOLDILOCKS = 4 };
+
+// Kind 4: schoolbook, 256 MACs per product and 136 per square, plus 18 for the fold.  (Karatsuba over phi would be 192,
+// but its middle product (a_lo + a_hi)(b_lo + b_hi) - a_lo b_lo has to leave the columns by subtraction -- signed
+// columns or a carry chain per half -- and its operands are a bit wider; with every column holding at most 16 products
+// the schoolbook form instead has room for K1 K2 = 15, which takes every weak reduction out of the X448 ladder step.)
+// Column budget, in units of 2^56 = one product of limbs below 2^28:
+//   upper column 16 + j   at most 15 products of K1 K2 each, the carry in
+//   lower column c        at most 16 products of K1 K2 each, the fold h_c + h_(c+8) or h_(c-8) + 2 h_c (digits below
+//                         2^28; h_15, the upper chain's last carry, below K1 K2 2^28 + 2^8: under 2^34 in all), the
+//                         carry in (below 2^36)
+// A "tight" limb of this kind is below 2^28 + SLACK: the tail adds what the lower chain leaves above limb 15 (weight
+// 2^448 again) to limbs 0 and 8 and lets the two carries of that (below 2^9) rest on limbs 1 and 9.
+struct UGold {
+  static constexpr int WORST = 16;  // products in the fullest column (c = 15)
+  static constexpr uint64_t SLACK = (uint64_t)1 << 10;
+  static constexpr uint64_t limb(int k) { return (uint64_t)k * (((uint64_t)1 << 28) + SLACK); }  // limbs of bound K stay below this
+  // WORST products, the fold terms and the carry in fit a 64-bit column; h_15 fits a register
+  static constexpr bool col_ok(int k1, int k2) {
+    return limb(k1) < ((uint64_t)1 << 32) && limb(k2) < ((uint64_t)1 << 32) &&
+           (unsigned __int128)WORST * limb(k1) * limb(k2) + ((uint64_t)1 << 36) + ((uint64_t)1 << 34) < ((unsigned __int128)1 << 64) &&
+           (unsigned __int128)limb(k1) * limb(k2) + ((unsigned __int128)1 << 36) < ((unsigned __int128)1 << (32 + 28));
+  }
+};
 
 template <class C, int K, int V>
 struct U {
@@ -110,10 +137,17 @@ struct UB {
   // (kind 3: N products + one folded digit times 1216)
   // (sparse reduction: the columns are signed, one bit less)
   static constexpr bool SPARSE = C::KIND == UK_MONT_PP1 && C::SPARSE_N > 0;
-  static constexpr int KKMAX = WRAPPED  ? (int)(~(uint64_t)0 / ((uint64_t)(2 * C::N - 1) * COL))
+  static constexpr bool GOLD = C::KIND == UK_GOLDILOCKS;
+  // (kind 4: N products, the fold's digits and the carry: UGold)
+  static constexpr int KKMAX = GOLD     ? 15
+                               : WRAPPED  ? (int)(~(uint64_t)0 / ((uint64_t)(2 * C::N - 1) * COL))
                                : SPARSE ? (int)((~(uint64_t)0 >> 1) / ((uint64_t)C::N * COL)) - 1
                                         : (int)(~(uint64_t)0 / ((uint64_t)C::N * COL)) - 1;
   static_assert(KKMAX >= 1, "limbs too wide for this many columns");
+  // kind 4, with the slack of its tight limbs and the carry in: every split of KKMAX fits, KKMAX + 1 does not
+  static_assert(!GOLD || (C::N == 16 && C::B == 28 && UGold::col_ok(1, 15) && UGold::col_ok(3, 5) && UGold::col_ok(5, 3) &&
+                          UGold::col_ok(15, 1) && !UGold::col_ok(4, 4)),
+                "Goldilocks columns: 16 products + fold digits + carry must stay below 2^64");
   static constexpr bool kk_ok(int k1, int k2) { return k1 * k2 <= KKMAX; }
   // squares also shift the operand left by one (two for the wrapped cross terms)
   static constexpr int KSQ_SHIFT = WRAPPED ? 2 : 1;
@@ -122,7 +156,7 @@ struct UB {
   static constexpr int vout(int v1, int v2) {
     return LO32   ? (int)((uint32_t)(v1 * v2) / C::RP) + 2
            : MONT ? (int)(((uint32_t)(v1 * v2) + C::RP - 1) / C::RP) + 1
-                  : (C::KIND == UK_PM19 ? 2 : 3);
+                  : ((C::KIND == UK_PM19 || GOLD) ? 2 : 3);  // kind 4: below 2^448 (1 + 2^-18) < 2p
   }
   // laziest limb bound a value may have and still be squared / multiplied by a tight value
   static constexpr int KLAZY = ksq_ok(2) ? 2 : 1;
@@ -738,9 +772,86 @@ ECCX_DEV void u_mul_core_pm(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], cons
   for (int i = 0; i < N; ++i) r[i] = t[i];
 }
 
+// 2^448 - 2^224 - 1 (kind 4): tail shared by the product and the small multiple.  t holds exact digits, c (below 2^36)
+// what the column chain left above them, of weight 2^448 = 2^224 + 1: it is added to limbs 0 and 8, whose carries
+// (below 2^9) stay on limbs 1 and 9.  The value is below 2^448 + 2^(28 + 9) + 2^(252 + 9) < 2p.
+template <class C>
+ECCX_DEV void u_gold_tail(uint32_t (&t)[C::N], uint64_t c) {
+  constexpr int H = C::PHI_LIMB;
+  static_assert(C::KIND == UK_GOLDILOCKS && C::N == 2 * H && C::B * C::N == C::PBITS, "phi on the middle limb boundary");
+  uint64_t lo = c + t[0], hi = c + t[H];
+  t[0] = (uint32_t)lo & C::MASK;
+  t[1] += (uint32_t)(lo >> C::B);
+  t[H] = (uint32_t)hi & C::MASK;
+  t[H + 1] += (uint32_t)(hi >> C::B);
+}
+
+// Goldilocks product / square (kind 4): the upper columns 16..30 first, carried into digits h[0..15] (h[15] the last
+// carry), then the lower columns, each taking the digits that fold onto it: 2^448 = 2^224 + 1 sends h_j to columns j
+// and j + 8, and for j >= 8 the latter wraps again to columns j - 8 and j.  Pairs of digits below 2^28 are added in
+// 32 bits and enter as one MAC by 1; h[15] may be as large as a limb product's top and goes in alone.
+template <class C, bool SQR, bool BCONST>
+ECCX_DEV void u_mul_core_gold(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N]) {
+  constexpr int N = C::N, H = C::PHI_LIMB;
+  uint32_t h[N], t[N], a2[N];
+  if constexpr (SQR) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) a2[i] = a[i] << 1;
+  }
+  UMacQ<BCONST> qa;
+  UMacQ<true> qf;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = N; k < 2 * N - 1; ++k) {
+    if constexpr (SQR) {
+#pragma unroll
+      for (int i = k - N + 1; 2 * i < k; ++i) qa.push(acc, a[i], a2[k - i]);
+      if ((k & 1) == 0) qa.push(acc, a[k / 2], a[k / 2]);
+    } else {
+#pragma unroll
+      for (int i = k - N + 1; i < N; ++i) qa.push(acc, a[i], b[k - i]);
+    }
+    qa.flush(acc);
+    h[k - N] = (uint32_t)acc & C::MASK;
+    acc >>= C::B;
+  }
+  h[N - 1] = (uint32_t)acc;
+  acc = 0;
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    if constexpr (SQR) {
+#pragma unroll
+      for (int i = 0; 2 * i < c; ++i) qa.push(acc, a[i], a2[c - i]);
+      if ((c & 1) == 0) qa.push(acc, a[c / 2], a[c / 2]);
+    } else {
+#pragma unroll
+      for (int i = 0; i <= c; ++i) qa.push(acc, a[i], b[c - i]);
+    }
+    qa.flush(acc);
+    if (c < H - 1) {
+      qf.push(acc, h[c] + h[c + H], 1u);
+    } else if (c == H - 1) {
+      qf.push(acc, h[c], 1u);
+      qf.push(acc, h[N - 1], 1u);
+    } else if (c < N - 1) {
+      qf.push(acc, h[c - H] + (h[c] << 1), 1u);
+    } else {
+      qf.push(acc, h[c - H], 1u);
+      qf.push(acc, h[N - 1], 2u);
+    }
+    qf.flush(acc);
+    t[c] = (uint32_t)acc & C::MASK;
+    acc >>= C::B;
+  }
+  u_gold_tail<C>(t, acc);
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = t[i];
+}
+
 template <class C, bool SQR, bool BCONST>
 ECCX_DEV void u_mul_core(uint32_t (&r)[C::N], const uint32_t (&a)[C::N], const uint32_t (&b)[C::N]) {
-  if constexpr (C::KIND == UK_MERSENNE) u_mul_core_mers<C, SQR, BCONST>(r, a, b);
+  if constexpr (C::KIND == UK_GOLDILOCKS) u_mul_core_gold<C, SQR, BCONST>(r, a, b);
+  else if constexpr (C::KIND == UK_MERSENNE) u_mul_core_mers<C, SQR, BCONST>(r, a, b);
   else if constexpr (C::KIND == UK_PM19) u_mul_core_pm<C, SQR, BCONST>(r, a, b);
   else u_mul_core_mont<C, SQR, BCONST>(r, a, b);
 }
@@ -757,7 +868,30 @@ ECCX_DEV U<C, 1, 3> u_reduce(const U<C, K1, V1>& a) {
   if constexpr (C::QMUL != 0) q = __umulhi(top, C::QMUL);
   else q = top >> C::TOPSHIFT;
   U<C, 1, 3> r;
-  if constexpr (C::KIND == UK_MERSENNE || C::KIND == UK_PM19) {
+  if constexpr (C::KIND == UK_GOLDILOCKS) {
+    // Two plain 32-bit chains.  The first leaves exact digits d and the carry c1 <= 16 out of limb 15 (limbs are below
+    // 16 * 2^28); c1 * 2^448 = c1 * (2^224 + 1) goes back in at limbs 0 and 8 and the second chain carries it through.
+    // Limbs 0..14 come out exact; limb 15 keeps the last carry and is 2^28 exactly in the one case it occurs (the
+    // value is then 2^448 + e with e < 2^230), so the value is below 2^448 + 2^230 < 2p, never 2p, and equal to 0 or
+    // p only with the digits of 0 or p: what u_is_zero_mod_p compares.  A second u_reduce leaves a value below 2^448.
+    (void)q;
+    constexpr int H = C::PHI_LIMB;
+    uint32_t d[N], c = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const uint32_t t = a.v[i] + c;
+      d[i] = t & C::MASK;
+      c = t >> C::B;
+    }
+    const uint32_t c1 = c;
+#pragma unroll
+    for (int i = 0; i < N - 1; ++i) {
+      const uint32_t t = d[i] + c + (i == H ? c1 : 0u);
+      r.v[i] = t & C::MASK;
+      c = t >> C::B;
+    }
+    r.v[N - 1] = d[N - 1] + c;
+  } else if constexpr (C::KIND == UK_MERSENNE || C::KIND == UK_PM19) {
     // q * p = q * 2^PBITS - q * (2^PBITS - p): q (or 19 q) enters at the bottom, q << TOPSHIFT
     // leaves at the top; every partial sum is non-negative and below 2^32, so the chain is
     // plain 32-bit arithmetic
@@ -1000,10 +1134,10 @@ ECCX_DEV U<C, 1, 2> u_mul_k_exit(const U<C, 1, 3>& a, const uint32_t (&k)[C::N])
   return r;
 }
 
-// multiply by a small constant k < 2^20 (kind 3 only: the ladder's (A + 2) / 4): one mad per limb
+// multiply by a small constant k < 2^20 (kinds 3 and 4: the ladders' (A + 2) / 4): one mad per limb
 template <class C, int K1, int V1>
 ECCX_DEV U<C, 1, 2> u_mul_small(const U<C, K1, V1>& a, uint32_t k) {
-  static_assert(C::KIND == UK_PM19, "written for 2^255 - 19");
+  static_assert(C::KIND == UK_PM19 || C::KIND == UK_GOLDILOCKS, "written for 2^255 - 19 and 2^448 - 2^224 - 1");
   constexpr int N = C::N;
   uint32_t t[N];
   uint64_t acc = 0;
@@ -1013,7 +1147,8 @@ ECCX_DEV U<C, 1, 2> u_mul_small(const U<C, K1, V1>& a, uint32_t k) {
     t[i] = (uint32_t)acc & C::MASK;
     acc >>= C::B;
   }
-  u_pm_tail<C>(t, acc);
+  if constexpr (C::KIND == UK_GOLDILOCKS) u_gold_tail<C>(t, acc);  // acc < 2^(32 + 20 - 28)
+  else u_pm_tail<C>(t, acc);
   U<C, 1, 2> r;
 #pragma unroll
   for (int i = 0; i < N; ++i) r.v[i] = t[i];

@@ -20,6 +20,7 @@ MIRROR_REFERENCE = 1 << 1
 TABLE_IN_LDS = 1 << 2
 TABLE_IN_L2 = 1 << 3
 X25519_RAW_LADDER = 1 << 4
+X448_RAW_LADDER = 1 << 4
 SUBTRACT = 1 << 5
 CHECK_SUBGROUP = 1 << 6
 UNCOMPRESSED = 1 << 7
@@ -36,6 +37,7 @@ PREP_ED25519_SIGN = 512
 PREP_ECDSA_SIGN = 1024
 PREP_H2C = 2048
 PREP_PAIRING = 4096
+PREP_X448 = 8192
 PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
@@ -151,20 +153,21 @@ class Engine:
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
-                h2c: bool = False, pairing: bool = False):
+                h2c: bool = False, pairing: bool = False, x448: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
         row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key; h2c: the row buffer
         hash_to_g1 works in (curve "bls12_381_g1") or hash_to_g2 (curve "bls12_381_g2": two rows per unit); pairing: the
-        slab and rows of pairing / pairing_check (curve "bls12_381_g2") for every shape with n * max(pairs, 1) <= max_n."""
+        slab and rows of pairing / pairing_check (curve "bls12_381_g2") for every shape with n * max(pairs, 1) <= max_n;
+        x448: the row buffer of x448 / x448_t (any curve: X448 has no id of its own) and, with host, its host-buffer copies."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
                                            | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)
                                            | (PREP_ED25519_SIGN if ed25519_sign else 0)
                                            | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)
-                                           | (PREP_PAIRING if pairing else 0)))
+                                           | (PREP_PAIRING if pairing else 0) | (PREP_X448 if x448 else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -757,6 +760,20 @@ class Engine:
         self._check(rc)
         return out.raw[: n * 32], flags.raw[:n]
 
+    def x448(self, scalars: bytes, u: Optional[bytes] = None, *, raw_ladder: bool = False):
+        """X448 over a batch: returns (n x 56 little-endian u-coordinates, flags).
+        Default: RFC 7748 semantics (protocol::x448::x448): little-endian scalars, clamped;
+        raw_ladder=True: MontgomeryPoint::scale_bytes, big-endian scalars used as given.
+        u=None multiplies the base point u = 5.  flags[i] = 1 where the result is zero."""
+        if len(scalars) % 56 or (u is not None and len(u) != len(scalars)):
+            raise ValueError("scalars / u must be n x 56 bytes")
+        n = len(scalars) // 56
+        out = ctypes.create_string_buffer(max(1, n * 56))
+        flags = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.eccx_x448(self._ctx, n, scalars, u, out, flags, X448_RAW_LADDER if raw_ladder else 0)
+        self._check(rc)
+        return out.raw[: n * 56], flags.raw[:n]
+
     def point_add_t(self, curve, a, b, out=None, flags=None, *, a_inf=None, b_inf=None, subtract: bool = False,
                     mirror: bool = False, stream: Optional[int] = None):
         """Device-tensor form of point_add (torch.uint8 CUDA tensors): out[i] = a[i] +- b[i]."""
@@ -818,6 +835,24 @@ class Engine:
             stream = torch.cuda.current_stream(scalars.device).cuda_stream
         rc = self._lib.eccx_x25519_dev(self._ctx, n, scalars.data_ptr(), u.data_ptr() if u is not None else None,
                                        out.data_ptr(), flags.data_ptr(), X25519_RAW_LADDER if raw_ladder else 0, stream)
+        self._check(rc)
+        return out, flags
+
+    def x448_t(self, scalars, u=None, out=None, flags=None, *, raw_ladder: bool = False,
+               stream: Optional[int] = None):
+        """Device-tensor form of x448 (torch.uint8 CUDA tensors, n x 56)."""
+        import torch
+
+        n = self._units(scalars, 56, "scalars")
+        if out is None:
+            out = torch.empty((n, 56), dtype=torch.uint8, device=scalars.device)
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.uint8, device=scalars.device)
+        self._tensors(n, ("scalars", scalars, 56), ("u", u, 56), ("out", out, 56), ("flags", flags, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(scalars.device).cuda_stream
+        rc = self._lib.eccx_x448_dev(self._ctx, n, scalars.data_ptr(), u.data_ptr() if u is not None else None,
+                                     out.data_ptr(), flags.data_ptr(), X448_RAW_LADDER if raw_ladder else 0, stream)
         self._check(rc)
         return out, flags
 

@@ -33,6 +33,7 @@
  *   eccx_pairing[_dev], eccx_pairing_check[_dev]  pairing, multi_miller_loop(..).final_exponentiation()
  *                              src/curve/bls12_381/pairing.rs:166-197, 263-272, 334, 360, 616-626
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
+ *   eccx_x448[_dev]            MontgomeryPoint ladder / x448     src/curve/curve448.rs:263-330, src/protocol/x448.rs:16-49
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
  *   eccx_point_decompress[_dev]  PointAffine::decompress, from_compressed[_oncurve_only],
  *                              from_uncompressed[_oncurve_only], decode_point
@@ -81,6 +82,8 @@
  * mark the unit, from the point alone, and it is redone by the reference-mirroring scan kernel; which units those
  * are is visible in timing.  ECCX_CT_GATHER (opt-in, fixed base) replaces the scan by a cross-lane register
  * gather; see the option.  eccx_x25519 is uniform by construction (conditional swaps are selects, no table).
+ * So is eccx_x448: the same ladder, 448 steps; the conditional branches of its kernel are loop counters and batch
+ * bounds (profiles/x448_isa_ct.txt).
  * What was MEASURED (tools/ct_trace_check.py, profiles/r03_ct_instruction_counts.json): six scalar sets -- random,
  * all zero, all ones, n - 1, one scalar repeated, random again -- execute exactly the same number of vector, scalar,
  * memory and LDS instructions in every secret-scalar kernel and the same busy cycles to 1-3 %.  Their DURATIONS are
@@ -179,6 +182,7 @@ enum {
                                      DESIGN.md for the numbers. */
   ECCX_TABLE_IN_L2 = 1u << 3,    /* fixed base: the reference's 4-bit comb, table read through L1/L2 */
   ECCX_X25519_RAW_LADDER = 1u << 4, /* eccx_x25519: raw MontgomeryPoint::scale_bytes semantics */
+  ECCX_X448_RAW_LADDER = 1u << 4,   /* eccx_x448: the same for curve448 (the same bit: each entry point knows it by its own name) */
   ECCX_SUBTRACT = 1u << 5,         /* eccx_point_add: compute a - b */
   ECCX_CHECK_SUBGROUP = 1u << 6,   /* eccx_point_decompress, bls12_381_g1: reject points outside G1 */
   ECCX_UNCOMPRESSED = 1u << 7,     /* eccx_point_[de]compress, bls12_381_g1: the 96-byte zcash flavour */
@@ -240,6 +244,9 @@ enum {
   ECCX_PREP_PAIRING = 1u << 12, /* eccx_reserve (bls12_381_g2): the slab and the rows of eccx_pairing / eccx_pairing_check for
                                    every shape with n * max(pairs, 1) <= max_n: 4 KB per resident lane, and 672 bytes per
                                    unit and per term */
+  ECCX_PREP_X448 = 1u << 13,    /* eccx_reserve (any valid curve id: X448 has none of its own): the row buffer of eccx_x448 for
+                                   max_n units (192 bytes each); with ECCX_PREP_HOST the copies of the host form's scalars, u,
+                                   out (56 bytes per unit each) and flags */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -561,6 +568,27 @@ int eccx_x25519(eccx_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* 
                 uint32_t opts);
 int eccx_x25519_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,
                     uint32_t opts, void* stream);
+
+/* X448: the curve448 x-only Montgomery ladder (RFC 7748), 448 steps, a24 = 39082.
+ *   default            protocol::x448::x448 (src/protocol/x448.rs:34-43): `scalars` are n x 56 little-endian
+ *                      RFC 7748 scalars, clamped on use (k[0] &= 252, k[55] |= 128, x448.rs:16-20); every bit
+ *                      of each u-coordinate is taken (decode_u, :24-27: the field is 448 bits wide).
+ *   ECCX_X448_RAW_LADDER  MontgomeryPoint::scale_bytes (src/curve/curve448.rs:320-330 -> ladder :263-302):
+ *                      `scalars` are the n x 56 BIG-endian strings the ladder consumes, no clamping.
+ *   u    : n x 56 little-endian u-coordinates, or NULL for the base point u = 5 (x448_base, x448.rs:47-49).
+ *          Any 56-byte string is accepted and taken modulo p = 2^448 - 2^224 - 1, in both modes.
+ *   out  : n x 56 little-endian u-coordinates of the results, canonical (below p)
+ *   flags: 1 where the result is zero (low-order input -- u = 0, 1, p - 1 and their non-canonical forms under a clamped
+ *          scalar -- or a raw scalar that is a multiple of the point's order: callers doing Diffie-Hellman must reject
+ *          it, x448.rs:32-33, :97-101), else 0
+ * Any option bit other than ECCX_X448_RAW_LADDER is refused with ECCX_ERR_ARG before anything is launched or written.
+ * There is no curve id for curve448: the reference has no group law or scalar field for it (curve448.rs:14-18).  The _dev
+ * form enqueues on `stream` without synchronising and uses the context's row buffer (grow-only; eccx_reserve with
+ * ECCX_PREP_X448 sizes it). */
+int eccx_x448(eccx_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* u, uint8_t* out, uint8_t* flags,
+              uint32_t opts);
+int eccx_x448_dev(eccx_ctx* ctx, size_t n, const void* d_scalars, const void* d_u, void* d_out, void* d_flags,
+                  uint32_t opts, void* stream);
 
 /* Point wire formats, batched: compressed encodings <-> the affine x||y records above.
  *   p256r1 / p384r1 / p521r1  SEC1 compressed, FB + 1 bytes: 0x02 | (y odd), then x big-endian;

@@ -35,6 +35,7 @@ pub const ECCX_MIRROR_REFERENCE: u32 = 1 << 1;
 pub const ECCX_TABLE_IN_LDS: u32 = 1 << 2;
 pub const ECCX_TABLE_IN_L2: u32 = 1 << 3;
 pub const ECCX_X25519_RAW_LADDER: u32 = 1 << 4;
+pub const ECCX_X448_RAW_LADDER: u32 = 1 << 4;
 pub const ECCX_SUBTRACT: u32 = 1 << 5;
 pub const ECCX_CHECK_SUBGROUP: u32 = 1 << 6;
 pub const ECCX_UNCOMPRESSED: u32 = 1 << 7;
@@ -61,6 +62,7 @@ pub const ECCX_PREP_ED25519_SIGN: u32 = 1 << 9; // eccx_ed25519_sign's working s
 pub const ECCX_PREP_ECDSA_SIGN: u32 = 1 << 10; // eccx_ecdsa_sign's / eccx_ecdsa_public_key's working slab
 pub const ECCX_PREP_H2C: u32 = 1 << 11; // eccx_hash_to_g1's / eccx_hash_to_g2's result rows
 pub const ECCX_PREP_PAIRING: u32 = 1 << 12; // eccx_pairing's / eccx_pairing_check's slab and rows
+pub const ECCX_PREP_X448: u32 = 1 << 13; // eccx_x448's result rows (any curve id) and, with ECCX_PREP_HOST, its copies
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -185,6 +187,12 @@ extern "C" {
                        opts: u32) -> c_int;
     pub fn eccx_x25519_dev(ctx: *mut eccx_ctx, n: usize, d_scalars: *const c_void, d_u: *const c_void,
                            d_out: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+
+    // X448 over a batch                                      protocol::x448::x448
+    pub fn eccx_x448(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,
+                     opts: u32) -> c_int;
+    pub fn eccx_x448_dev(ctx: *mut eccx_ctx, n: usize, d_scalars: *const c_void, d_u: *const c_void,
+                         d_out: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
 
     // wire formats: SEC1 compressed (sec2), zcash (G1), RFC 8032 (ed25519)
     pub fn eccx_compressed_bytes(curve: c_int) -> c_int;

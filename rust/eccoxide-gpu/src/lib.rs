@@ -38,6 +38,7 @@ pub mod ecdsa;
 pub mod ed25519;
 pub mod pairing;
 pub mod x25519;
+pub mod x448;
 
 use core::ffi::{c_int, CStr};
 use std::fmt;
@@ -161,6 +162,14 @@ impl GpuContext {
         // the batch functions of this crate call the host-buffer entry points: their device-side copies too
         self.check(unsafe {
             ffi::eccx_reserve(self.raw, curve.id(), max_n, ffi::ECCX_PREP_VAR | ffi::ECCX_PREP_CT | ffi::ECCX_PREP_HOST)
+        })
+    }
+
+    /// Size the row buffer and the host-buffer copies of `x448::x448_batch` for up to `max_n` units.  X448 has no curve
+    /// id (`ECCX_PREP_X448` is honoured with any valid one).
+    pub fn reserve_x448(&self, max_n: usize) -> Result<(), GpuError> {
+        self.check(unsafe {
+            ffi::eccx_reserve(self.raw, Curve::Ed25519.id(), max_n, ffi::ECCX_PREP_X448 | ffi::ECCX_PREP_HOST)
         })
     }
 

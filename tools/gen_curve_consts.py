@@ -152,10 +152,10 @@ def arr(name, vals):
     return "  static constexpr uint32_t %s[%d] = {%s};" % (name, len(vals), body)
 
 
-def emit_field(out, p, L, mersenne=0, pm19=0):
+def emit_field(out, p, L, mersenne=0, pm19=0, plain=False):
     # Mersenne (2^k - 1) and pseudo-Mersenne (2^255 - 19) fields are kept in plain
-    # (non-Montgomery) form: R = 1
-    R = 1 if (mersenne or pm19) else 1 << (32 * L)
+    # (non-Montgomery) form: R = 1; so is 2^448 - 2^224 - 1 (plain)
+    R = 1 if (mersenne or pm19 or plain) else 1 << (32 * L)
     out.append("  static constexpr int MERSENNE = %d;  // k if p = 2^k - 1 (plain representation, fold reduction), else 0" % mersenne)
     out.append("  static constexpr int PM19 = %d;  // 1 if p = 2^255 - 19 (plain representation, fold by 38), else 0" % pm19)
     out.append(arr("P", limbs(p, L)))
@@ -212,6 +212,7 @@ def emit_unsat(out, name, sat_name, p, gx, gy, bits, n, kind, extra=(), solinas=
     kind 1: Montgomery, general p (m = acc * N0B mod 2^bits)
     kind 2: p = 2^k - 1, plain representation, 2^(bits*n) = 2^(bits*n - k) mod p folded into the product
     kind 3: p = 2^255 - 19, plain representation, 2^(bits*n) = 19 * 2^(bits*n - 255) mod p
+    (kind 4, 2^448 - 2^224 - 1, has an emitter of its own: emit_goldilocks)
     BIAS is 4p written with every limb >= 2^bits - 1 (the largest tight limb) so that
     a + BIAS - b never borrows for tight b < 3p."""
     mont = kind in (0, 1)
@@ -305,6 +306,62 @@ def emit_unsat(out, name, sat_name, p, gx, gy, bits, n, kind, extra=(), solinas=
     out.append("  static constexpr uint32_t ROOT_EXP[%d] = {%s};" % (nw, ", ".join("0x%08xu" % ((root_exp >> (32 * i)) & 0xFFFFFFFF) for i in range(nw))))
     out.append("};")
     out.append("")
+
+
+P448 = 2**448 - 2**224 - 1
+X448_A24 = 39082  # (156326 + 2) / 4: the ladder adds a24 * E to BB (RFC 7748 section 5 writes AA + 39081 * E)
+X448_U = 5        # the base point's u
+
+
+def emit_goldilocks(out):
+    """CURVE448 / CURVE448U: p = 2^448 - 2^224 - 1 in plain representation, 16 limbs of 28 bits (kind 4, ufe.hpp).
+    phi = 2^224 is the boundary of limb 8 and 2^448 = phi + 1 (mod p), so the product's columns 16..30 fold onto columns
+    0..14 and 8..22 inside the accumulators.  BIAS is 2p (not 4p: 4p does not fit 16 limbs below 2^29) spread so that
+    every limb is at least 2^28 + 2^27: a + BIAS - b has no negative limb for any b whose limbs stay below that, and is
+    non-negative as a value because such a b is below 2p."""
+    p, bits, n, L = P448, 28, 16, 14
+    assert p.bit_length() == 448 == bits * n == 32 * L
+    assert ((1 << 448) - (1 << 224) - 1) % p == 0 and ((1 << 448) % p) == (1 << 224) + 1
+    # prime (Miller-Rabin on fixed bases is enough for a constant everybody knows), p = 3 mod 4
+    assert p % 4 == 3 and all(pow(a, p - 1, p) == 1 for a in (2, 3, 5, 7, 11))
+    d = digits(2 * p, bits, n)
+    d[n - 1] = (2 * p) >> (bits * (n - 1))
+    bias = [d[0] + (1 << bits)] + [d[i] + (1 << bits) - 1 for i in range(1, n - 1)] + [d[n - 1] - 1]
+    assert sum(b << (bits * i) for i, b in enumerate(bias)) == 2 * p
+    assert all((1 << bits) + (1 << (bits - 1)) <= b < (1 << (bits + 1)) for b in bias)
+    out.append("")
+    out.append("struct CURVE448;")
+    out.append("struct CURVE448U {")
+    out.append("  using Sat = CURVE448;          // saturated twin (byte I/O, normalisation)")
+    out.append("  static constexpr int N = %d;     // limbs" % n)
+    out.append("  static constexpr int B = %d;    // bits per limb" % bits)
+    out.append("  static constexpr int KIND = 4;  // 4: 2^448 - 2^224 - 1 (plain), 2^448 = 2^224 + 1 folded inside the columns")
+    out.append("  static constexpr uint32_t FOLD = 0u;")
+    out.append("  static constexpr int PBITS = %d;" % p.bit_length())
+    out.append("  static constexpr int TOPSHIFT = %d;  // bit PBITS inside the top limb: the limb's whole width" % (448 - bits * (n - 1)))
+    out.append("  static constexpr uint32_t QMUL = 0x00000000u;")
+    out.append("  static constexpr uint32_t RP = 1u;  // plain representation")
+    out.append("  static constexpr uint32_t MASK = 0x%08xu;" % ((1 << bits) - 1))
+    out.append("  static constexpr uint32_t N0B = 0x%08xu;  // -p^-1 mod 2^B" % ((-pow(p, -1, 1 << bits)) % (1 << bits)))
+    out.append("  static constexpr int PHI_LIMB = %d;  // 2^224 = 2^(B * PHI_LIMB)" % (224 // bits))
+    out.append(arr("P", digits(p, bits, n)))
+    out.append(arr("PP1", digits(p + 1, bits, n)))
+    out.append(arr("P2", digits(p, bits, n)) + "  // 2p has 449 bits: a reduced value (below 2^448 + 2^226) is never 2p; p again")
+    out.append(arr("ONE", digits(1, bits, n)))
+    out.append(arr("R2", digits(1, bits, n)))
+    out.append(arr("BIAS", bias) + "  // 2p")
+    out.append(arr("RS", digits(1, bits, n)))
+    out.append("  static constexpr int SOL_N = 0;")
+    out.append("  static constexpr int SPARSE_N = 0;")
+    out.append(arr("GU", digits(X448_U, bits, n)) + "  // u of the base point")
+    out.append("  static constexpr uint32_t A24 = %du;  // (A + 2) / 4, A = 156326" % X448_A24)
+    out.append("};")
+    out.append("struct CURVE448 {")
+    out.append("  static constexpr int L = %d;" % L)
+    out.append("  static constexpr int FB = 56;")
+    out.append("  static constexpr int SB = 56;")
+    emit_field(out, p, L, 0, 0, plain=True)
+    out.append("};")
 
 
 def emit_sat(out, name, p, b, gx, gy, fb, sb, a0):
@@ -671,6 +728,7 @@ def main():
     emit_bls_g2(out)
     emit_bls_g2_h2c(out)
     emit_bls_pairing(out)
+    emit_goldilocks(out)
     sys.stdout.write("\n".join(out) + "\n")
 
 
