@@ -22,7 +22,7 @@ namespace {
 
 using eccx::CurveOps;
 
-constexpr int NCURVES = 8;  // curve ids 0 .. 7 (6 is unassigned)
+constexpr int NCURVES = 10;  // curve ids 0 .. 9 (6 and 8 are unassigned)
 // internal kernel option bits (kernels.hpp)
 constexpr uint32_t K_BASE_IS_GENERATOR = 1u << 0;
 constexpr uint32_t K_OUT_TABLE = 1u << 1;
@@ -41,6 +41,7 @@ const CurveOps* ops_of(int curve) {
     case ECCX_ED25519: return &eccx::ops_ED25519();
     case ECCX_P256K1: return &eccx::ops_P256K1();
     case ECCX_BLS12_381_G2: return &eccx::ops_BLS12_381_G2();
+    case ECCX_JUBJUB: return &eccx::ops_JUBJUB();
     default: return nullptr;
   }
 }
@@ -519,6 +520,13 @@ int mirror_only_err(eccx_ctx* ctx, const CurveOps* ops, const void* proj, uint32
   return ECCX_OK;
 }
 
+// A curve whose table says strict_opts (jubjub) refuses the options it has no kernel for, where the older curves fall
+// back to another kernel that returns the same bytes
+int strict_err(eccx_ctx* ctx, const CurveOps* ops, uint32_t opts, uint32_t unserved) {
+  if (!ops->strict_opts || !(opts & unserved)) return ECCX_OK;
+  return arg_err(ctx, "jubjub: ECCX_TABLE_IN_LDS, ECCX_CT_GATHER, ECCX_CHECK_SUBGROUP and ECCX_ASSUME_SUBGROUP are not served");
+}
+
 uint32_t kopts_of(uint32_t opts) { return (opts & ECCX_VALIDATE_POINTS) ? K_VALIDATE : 0u; }
 
 size_t proj_bytes(const CurveOps* ops) { return (size_t)(ops->info.edwards ? 4 : 3) * ops->info.fb; }
@@ -926,6 +934,7 @@ int eccx_scalarmul_var_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_sca
   const CurveOps* ops;
   if (int rc = enter(ctx, curve, &ops)) return rc;
   if (int rc = mirror_only_err(ctx, ops, d_proj, opts, 0)) return rc;
+  if (int rc = strict_err(ctx, ops, opts, ECCX_ASSUME_SUBGROUP | ECCX_CHECK_SUBGROUP | ECCX_CT_GATHER | ECCX_TABLE_IN_LDS)) return rc;
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_scalars && d_points && d_out && d_flags)) return rc;
   // ECCX_CT_SCAN: the reference-mirroring ladder (complete formulas, no data-dependent branch) with
@@ -951,6 +960,7 @@ int eccx_scalarmul_base_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_sc
   const CurveOps* ops;
   if (int rc = enter(ctx, curve, &ops)) return rc;
   if (int rc = mirror_only_err(ctx, ops, d_proj, opts, ECCX_TABLE_IN_LDS | ECCX_TABLE_IN_L2 | ECCX_CT_GATHER)) return rc;
+  if (int rc = strict_err(ctx, ops, opts, ECCX_ASSUME_SUBGROUP | ECCX_CHECK_SUBGROUP | ECCX_CT_GATHER | ECCX_TABLE_IN_LDS)) return rc;
   if (n == 0) return ECCX_OK;
   if (int rc = begin_batch(ctx, d_scalars && d_out && d_flags)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
@@ -1073,7 +1083,7 @@ int eccx_point_decompress_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_
   if (!d_enc || !d_out || !d_flags) return arg_err(ctx, "null buffer");
   // the sec2 curves have cofactor 1 (nothing to check); decode_point makes no such test
   if ((opts & ECCX_CHECK_SUBGROUP) && ops->info.edwards)
-    return arg_err(ctx, "ECCX_CHECK_SUBGROUP: edwards25519 decoding makes no subgroup test");
+    return arg_err(ctx, "ECCX_CHECK_SUBGROUP: edwards25519 and jubjub decoding make no subgroup test");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint8_t* enc = static_cast<const uint8_t*>(d_enc);

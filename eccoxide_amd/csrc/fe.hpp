@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace eccx {
 
 #define ECCX_DEV __device__ __forceinline__
@@ -462,6 +464,26 @@ ECCX_DEV void fe_store_le(uint8_t* __restrict__ out, const Fe<C::L>& a) {
     }
   }
 }
+
+// Byte order of a curve class's field elements on the wire: little-endian unless the class says IO_BE (jubjub, whose
+// reference types are big-endian throughout: from_bytes_unchecked_be, src/params/jubjub.rs).  What the twisted
+// Edwards kernels load and store with.
+template <class C, class = void>
+struct fe_io_be : std::false_type {};
+template <class C>
+struct fe_io_be<C, std::void_t<decltype(C::IO_BE)>> : std::bool_constant<C::IO_BE> {};
+// Macros rather than functions so that the edwards25519 kernels are compiled from the statements they always had:
+// behind a function boundary hipcc schedules the surrounding code differently.
+#define ECCX_FE_LOAD_IO(C, r, in)                        \
+  {                                                      \
+    if constexpr (fe_io_be<C>::value) fe_load_be<C>(r, in); \
+    else fe_load_le<C>(r, in);                           \
+  }
+#define ECCX_FE_STORE_IO(C, out, a)                        \
+  {                                                        \
+    if constexpr (fe_io_be<C>::value) fe_store_be<C>(out, a); \
+    else fe_store_le<C>(out, a);                           \
+  }
 
 // value < P ?   (canonical-encoding check, field_macros.rs:604-627)
 template <class C>

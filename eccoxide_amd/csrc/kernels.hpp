@@ -217,17 +217,17 @@ ECCX_DEV void ed_store_result(size_t idx, const EdPt<C>& q, bool rejected, uint8
   bool neutral = fe_is_zero<C>(ax) && fe_eq<C>(ay, one);
   fe_from_mont<C>(t, ax);
   if (rejected) fe_zero<C>(t);
-  fe_store_le<C>(out + idx * 64, t);
+  ECCX_FE_STORE_IO(C, out + idx * 64, t);
   fe_from_mont<C>(t, ay);
   if (rejected) fe_zero<C>(t);
-  fe_store_le<C>(out + idx * 64 + 32, t);
+  ECCX_FE_STORE_IO(C, out + idx * 64 + 32, t);
   flags[idx] = rejected ? 2 : (neutral ? 1 : 0);
   if (proj) {
     uint8_t* pr = proj + idx * 128;
-    fe_from_mont<C>(t, q.x); fe_store_le<C>(pr, t);
-    fe_from_mont<C>(t, q.y); fe_store_le<C>(pr + 32, t);
-    fe_from_mont<C>(t, q.z); fe_store_le<C>(pr + 64, t);
-    fe_from_mont<C>(t, q.t); fe_store_le<C>(pr + 96, t);
+    fe_from_mont<C>(t, q.x); ECCX_FE_STORE_IO(C, pr, t);
+    fe_from_mont<C>(t, q.y); ECCX_FE_STORE_IO(C, pr + 32, t);
+    fe_from_mont<C>(t, q.z); ECCX_FE_STORE_IO(C, pr + 64, t);
+    fe_from_mont<C>(t, q.t); ECCX_FE_STORE_IO(C, pr + 96, t);
   }
 }
 
@@ -248,8 +248,8 @@ __global__ void __launch_bounds__(WG) k_ed_scalarmul_var(size_t n, const uint8_t
     fe_set<C>(p.y, C::GY);
   } else {
     Fe<L> rx, ry;
-    fe_load_le<C>(rx, points + idx * 64);
-    fe_load_le<C>(ry, points + idx * 64 + 32);
+    ECCX_FE_LOAD_IO(C, rx, points + idx * 64);
+    ECCX_FE_LOAD_IO(C, ry, points + idx * 64 + 32);
     fe_to_mont<C>(p.x, rx);
     fe_to_mont<C>(p.y, ry);
     if (opts & OPT_VALIDATE) {
@@ -389,12 +389,12 @@ __global__ void __launch_bounds__(WG) k_ed_point_add(size_t n, const uint8_t* __
   for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG) {
     EdPt<C> p, q, r;
     Fe<L> raw;
-    fe_load_le<C>(raw, a + i * 64); fe_to_mont<C>(p.x, raw);
-    fe_load_le<C>(raw, a + i * 64 + 32); fe_to_mont<C>(p.y, raw);
+    ECCX_FE_LOAD_IO(C, raw, a + i * 64); fe_to_mont<C>(p.x, raw);
+    ECCX_FE_LOAD_IO(C, raw, a + i * 64 + 32); fe_to_mont<C>(p.y, raw);
     fe_set<C>(p.z, C::ONE);
     fe_mul<C>(p.t, p.x, p.y);
-    fe_load_le<C>(raw, b + i * 64); fe_to_mont<C>(q.x, raw);
-    fe_load_le<C>(raw, b + i * 64 + 32); fe_to_mont<C>(q.y, raw);
+    ECCX_FE_LOAD_IO(C, raw, b + i * 64); fe_to_mont<C>(q.x, raw);
+    ECCX_FE_LOAD_IO(C, raw, b + i * 64 + 32); fe_to_mont<C>(q.y, raw);
     if (opts & OPT_NEGATE_B) fe_neg<C>(q.x, q.x);  // -(x, y) = (-x, y) (curve25519.rs:731-738)
     fe_set<C>(q.z, C::ONE);
     fe_mul<C>(q.t, q.x, q.y);

@@ -13,6 +13,7 @@
 //                              143-148,181-202,253-262).
 //   edwards25519               RFC 8032, 32 bytes: y little-endian, bit 255 = low bit of x
 //                              (src/protocol/ed25519.rs:27-59, curve25519.rs:765-784).
+//   jubjub                     the same packing (ZIP 216) of big-endian records; decoder in kernels_jubjub.hpp.
 //
 // Decompression needs one square root per point: a^((p+1)/4) for the four p = 3 (mod 4) fields
 // (sec2/p256r1.rs:68-84, p384r1.rs:71, p521r1.rs:126-131, bls12_381/fp.rs:64-68) and the
@@ -27,7 +28,7 @@
 namespace eccx {
 
 enum : uint8_t { CODEC_OK = 0, CODEC_INFINITY = 1, CODEC_INVALID = 2 };
-enum : int { FORMAT_SEC1 = 0, FORMAT_ZCASH = 1, FORMAT_RFC8032 = 2, FORMAT_ZCASH_RAW = 3 };
+enum : int { FORMAT_SEC1 = 0, FORMAT_ZCASH = 1, FORMAT_RFC8032 = 2, FORMAT_ZCASH_RAW = 3, FORMAT_JUBJUB = 4 };
 
 template <class CU>
 using UT = U<CU, 1, 3>;
@@ -259,6 +260,15 @@ __global__ void __launch_bounds__(WG) k_point_compress(size_t n, const uint8_t* 
         o[0] = is_inf ? 0x40u : p[0];
 #pragma unroll
         for (int k = 1; k < PB; ++k) o[k] = is_inf ? 0u : p[k];
+      } else if constexpr (FORMAT == FORMAT_JUBJUB) {
+        // the packed form of kernels_jubjub.hpp from big-endian x || y: y little-endian, x mod 2 (the low bit of the
+        // last byte of x) in bit 255; no infinity record either
+        static_assert(FB % 4 == 0, "word copies");
+        const uint32_t* pw = reinterpret_cast<const uint32_t*>(p);
+        uint32_t* ow = reinterpret_cast<uint32_t*>(o);
+        const uint32_t sign = (pw[FB / 4 - 1] >> 24) & 1u;
+#pragma unroll
+        for (int k = 0; k < FB / 4; ++k) ow[k] = __builtin_bswap32(pw[2 * (FB / 4) - 1 - k]) | (k == FB / 4 - 1 ? sign << 31 : 0u);
       } else {
         // y little-endian with the low bit of x in bit 255 (encode_point, ed25519.rs:27-36); the
         // identity is the ordinary point (0, 1), so there is no infinity record

@@ -66,8 +66,13 @@ namespace eccx {
 #ifndef ECCX_CT_GATHER_BITS
 #define ECCX_CT_GATHER_BITS 7
 #endif
+// twisted Edwards curve classes: edwards25519 by its field kind, any other (jubjub) by its saturated twin's EDWARDS
+template <class CU, class = void>
+struct ct_is_edwards : std::bool_constant<CU::KIND == UK_PM19> {};
+template <class CU>
+struct ct_is_edwards<CU, std::void_t<decltype(CU::Sat::EDWARDS)>> : std::bool_constant<CU::Sat::EDWARDS> {};
 template <class CU, bool GATHER = false>
-constexpr int ct_base_bits() { return GATHER ? ECCX_CT_GATHER_BITS : (CU::KIND == UK_PM19 ? ECCX_CT_BASE_BITS_ED : ECCX_CT_BASE_BITS); }
+constexpr int ct_base_bits() { return GATHER ? ECCX_CT_GATHER_BITS : (ct_is_edwards<CU>::value ? ECCX_CT_BASE_BITS_ED : ECCX_CT_BASE_BITS); }
 // waves per SIMD the comb is compiled for (the XYZZ accumulator is four coordinates)
 template <class CU>
 constexpr int ct_base_occupancy() { return CU::N <= 9 ? ECCX_CT_BASE_OCC9 : unsat_occupancy<CU>(); }
@@ -77,7 +82,7 @@ template <class CU, bool GATHER = false>
 constexpr int ct_base_entries() { return 1 << (ct_base_bits<CU, GATHER>() - 1); }
 // words per table entry, padded to 16 bytes: Weierstrass (x, y), edwards25519 (y - x, y + x, 2d x y)
 template <class CU>
-constexpr int ct_entry_words() { return (((CU::KIND == UK_PM19 ? 3 : 2) * CU::N + 3) / 4) * 4; }
+constexpr int ct_entry_words() { return (((ct_is_edwards<CU>::value ? 3 : 2) * CU::N + 3) / 4) * 4; }
 // windows (counted from the top) in which accumulator == +-entry is possible: those with W (w + 1) >= NBITS
 template <class CU, bool GATHER = false>
 constexpr int ct_unsafe_windows() {
@@ -440,9 +445,10 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_base_ct(size_t n, const 
       stage.template store<(ECCX_CT_SCAN_PK != 0)>(lds[0]);
       __syncthreads();
     }
+    [[maybe_unused]] const T one = ued_small<CU, 1>();  // digit 0: the neutral entry (1, 1, 0)
     T qx, qy, qz, qt;  // the neutral element (0, 1, 1, 0)
     u_set_zero(qx); u_set_zero(qy); u_set_zero(qz); u_set_zero(qt);
-    qy.v[0] = 1; qz.v[0] = 1;
+    ued_set_small<CU, 1>(qy); ued_set_small<CU, 1>(qz);
     for (int w = 0; w < NWIN; ++w) {
       if constexpr (STAGED) {
         if (w + 1 < NWIN) stage.load(gtab + (size_t)(w + 1) * SLICE4);
@@ -456,20 +462,25 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_base_ct(size_t n, const 
         // digit 0: the neutral element (1, 1, 0) instead of whatever lane ENT - 1 holds
         const uint64_t mz = ct_mask(d == 0);
 #pragma unroll
-        for (int i = 0; i < 3 * N; ++i) ct_cmov1(ew[i], (i == 0 || i == N) ? 1u : 0u, mz);
+        for (int i = 0; i < 3 * N; ++i) ct_cmov1(ew[i], i < 2 * N ? (UB<CU>::MONT ? one.v[i % N] : (i % N == 0 ? 1u : 0u)) : 0u, mz);
       } else {
 #pragma unroll
         for (int i = 0; i < EW; ++i) ew[i] = 0;
         if constexpr (STAGED && !ECCX_CT_SCAN_PK) {
-          ew[0] = 1;  // y - x
-          ew[N] = 1;  // y + x
+#pragma unroll
+          for (int i = 0; i < N; ++i) ew[i] = ew[N + i] = UB<CU>::MONT ? one.v[i] : (i == 0 ? 1u : 0u);  // y - x, y + x
           ct_scan_lds<EW, ENT>(ew, lds[w & 1], d);
         } else {
           if constexpr (STAGED) ct_scan_lds_pk<EW, ENT, 3 * N, CU::B>(ew, lds[w & 1], d);
           else ct_scan_smem<EW, ENT>(ew, gtab + (size_t)w * SLICE4, d);
           const uint64_t mz = ct_mask(d == 0);
-          ct_cmov1(ew[0], 1u, mz);
-          ct_cmov1(ew[N], 1u, mz);
+          if constexpr (UB<CU>::MONT) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) { ct_cmov1(ew[i], one.v[i], mz); ct_cmov1(ew[N + i], one.v[i], mz); }
+          } else {
+            ct_cmov1(ew[0], 1u, mz);
+            ct_cmov1(ew[N], 1u, mz);
+          }
         }
       }
       T a, b, t2d, ym, yp;
@@ -487,7 +498,7 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_base_ct(size_t n, const 
         qx = u_reduce(u_add(dx, dx));
         qy = u_reduce(u_add(sy, sy));
         u_set_zero(qz);
-        qz.v[0] = 4;
+        ued_set_small<CU, 4>(qz);
         qt = u_fit<1, 3>(u_mul(dx, sy));
       } else {
         ued_add_niels<CU, 2, 4>(qx, qy, qz, qt, ym, yp, t2);

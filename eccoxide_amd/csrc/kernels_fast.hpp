@@ -89,10 +89,10 @@ __global__ void __launch_bounds__(WG) k_batch_to_affine(size_t n, const uint32_t
           const bool neutral = fe_is_zero<C>(ax) && fe_eq<C>(ay, one);
           fe_from_mont<C>(t, ax);
           if (rejected) fe_zero<C>(t);
-          fe_store_le<C>(out + i * (size_t)(2 * FB), t);
+          ECCX_FE_STORE_IO(C, out + i * (size_t)(2 * FB), t);
           fe_from_mont<C>(t, ay);
           if (rejected) fe_zero<C>(t);
-          fe_store_le<C>(out + i * (size_t)(2 * FB) + FB, t);
+          ECCX_FE_STORE_IO(C, out + i * (size_t)(2 * FB) + FB, t);
           flags[i] = rejected ? 2 : (neutral ? 1 : 0);
         } else {
           const bool ok = present && !rejected;

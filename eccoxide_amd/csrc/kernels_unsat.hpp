@@ -759,6 +759,45 @@ __global__ void __launch_bounds__(WG, 4) k_x25519_ladder_unsat(size_t n, const u
   }
 }
 
+// ---- twisted Edwards curves (edwards25519, jubjub): what the kernels below need to know about the curve class ----
+// The small constants 1, 2 and 4 in the field's working form: the integer itself on a plain field (2^255 - 19), K * R
+// mod p on a Montgomery one (jubjub: CU::ONE added up and reduced, folded at compile time).
+// ued_set_small writes into a value the caller has set to zero (the statements the edwards25519 kernels always had).
+template <class CU, uint32_t K>
+ECCX_DEV U<CU, 1, 3> ued_small() {
+  static_assert(K == 1 || K == 2 || K == 4, "the constants the Edwards kernels use");
+  U<CU, 1, 3> r;
+  if constexpr (!UB<CU>::MONT) {
+    u_set_zero(r);
+    r.v[0] = K;
+  } else {
+    U<CU, 1, 1> one;
+#pragma unroll
+    for (int i = 0; i < CU::N; ++i) one.v[i] = CU::ONE[i];
+    if constexpr (K == 1) r = u_as<1, 3>(one);
+    else if constexpr (K == 2) r = u_reduce(u_add(one, one));
+    else r = u_reduce(u_add(u_add(one, one), u_add(one, one)));
+  }
+  return r;
+}
+template <class CU, uint32_t K>
+ECCX_DEV void ued_set_small(U<CU, 1, 3>& zeroed) {
+  if constexpr (!UB<CU>::MONT) zeroed.v[0] = K;
+  else zeroed = ued_small<CU, K>();
+}
+// affine coordinate bytes (plain canonical integer, saturated) -> working form: tight (DST a U<CU, 1, 2>), and reduced
+// to exact digits (DST a U<CU, 1, 3>).  Macros for the reason given at ECCX_FE_LOAD_IO (fe.hpp).
+#define ECCX_UED_FROM_PLAIN12(CU, dst, raw)                       \
+  {                                                               \
+    if constexpr (UB<CU>::MONT) dst = u_to_mont<CU>(raw);         \
+    else dst = u_from_sat<CU>(raw);                               \
+  }
+#define ECCX_UED_FROM_PLAIN(CU, dst, raw)                                              \
+  {                                                                                    \
+    if constexpr (UB<CU>::MONT) dst = u_reduce(u_as<1, 3>(u_to_mont<CU>(raw)));        \
+    else dst = u_reduce(u_as<1, 3>(u_from_sat<CU>(raw)));                              \
+  }
+
 // ---- edwards25519 fixed base, 16-bit windows, unsaturated field ------------------------------
 // The reference's mul_base (curve25519.rs:840-851) adds one table entry per 4-bit window; k*B
 // does not depend on the window width, so the default path uses 16-bit windows -- entry (w, d) =
@@ -817,7 +856,7 @@ ECCX_DEV void ued_comb_accumulate(U<CU, 1, 3>& qx, U<CU, 1, 3>& qy, U<CU, 1, 3>&
     qx = u_reduce(u_add(dx, dx));
     qy = u_reduce(u_add(sy, sy));
     u_set_zero(qz);
-    qz.v[0] = 4;
+    ued_set_small<CU, 4>(qz);
     qt = u_fit<1, 3>(u_mul(dx, sy));          // 4xy = X Y / Z
   }
   for (int w = FROM_NEUTRAL ? 1 : 0; w < comb_windows<CU>(); ++w) {
@@ -836,10 +875,11 @@ __global__ void k_ed_affine_to_niels_unsat(size_t entries, const uint8_t* __rest
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= entries) return;
   Fe<L> fx, fy;
-  fe_load_le<CS>(fx, affine + i * 64);
-  fe_load_le<CS>(fy, affine + i * 64 + 32);
-  const auto x = u_from_sat<CU>(fx);
-  const auto y = u_from_sat<CU>(fy);
+  ECCX_FE_LOAD_IO(CS, fx, affine + i * 64);
+  ECCX_FE_LOAD_IO(CS, fy, affine + i * 64 + 32);
+  U<CU, 1, 2> x, y;
+  ECCX_UED_FROM_PLAIN12(CU, x, fx);
+  ECCX_UED_FROM_PLAIN12(CU, y, fy);
   U<CU, 1, 2> d2;
 #pragma unroll
   for (int k = 0; k < N; ++k) d2.v[k] = CU::D2[k];
@@ -863,7 +903,7 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_base_unsat(size_t n, con
     const uint8_t* __restrict__ k = scalars + idx * 32;
     T qx, qy, qz, qt;  // the neutral element (0, 1, 1, 0)
     u_set_zero(qx); u_set_zero(qy); u_set_zero(qz); u_set_zero(qt);
-    qy.v[0] = 1; qz.v[0] = 1;
+    ued_set_small<CU, 1>(qy); ued_set_small<CU, 1>(qz);
     ued_comb_accumulate<CU, true>(qx, qy, qz, qt, k, table);
     if (active) {
       u3_store<CU>(rows_out + idx * (size_t)urow3_words<CU>(), qx, qy, qz);
@@ -1052,8 +1092,8 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_var_unsat(size_t n, cons
       for (int i = 0; i < N; ++i) { p.x.v[i] = CU::GX[i]; p.y.v[i] = CU::GY[i]; }
     } else {
       Fe<L> rx, ry;
-      fe_load_le<CS>(rx, points + idx * 64);
-      fe_load_le<CS>(ry, points + idx * 64 + 32);
+      ECCX_FE_LOAD_IO(CS, rx, points + idx * 64);
+      ECCX_FE_LOAD_IO(CS, ry, points + idx * 64 + 32);
       if (opts & OPT_VALIDATE) {
         // -x^2 + y^2 == 1 + d x^2 y^2  <=>  2(y^2 - x^2 - 1) == 2d x^2 y^2  (curve25519.rs:649-660),
         // on the saturated twin
@@ -1070,14 +1110,14 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_var_unsat(size_t n, cons
         fe_mul_k<CS>(rhs, rhs, CS::D2);
         rejected = !(fe_is_canonical<CS>(rx) && fe_is_canonical<CS>(ry) && fe_eq<CS>(lhs, rhs));
       }
-      p.x = u_reduce(u_as<1, 3>(u_from_sat<CU>(rx)));
-      p.y = u_reduce(u_as<1, 3>(u_from_sat<CU>(ry)));
+      ECCX_UED_FROM_PLAIN(CU, p.x, rx);
+      ECCX_UED_FROM_PLAIN(CU, p.y, ry);
     }
     if constexpr (FUSED) {
       if (opts & OPT_NEGATE_B) p.x = u_reduce(u_neg(p.x));  // -(x, y) = (-x, y) (curve25519.rs:731-738)
     }
     u_set_zero(p.z);
-    p.z.v[0] = 1;
+    ued_set_small<CU, 1>(p.z);
     p.t = u_fit<1, 3>(u_mul(p.x, p.y));  // from_affine (curve25519.rs:638-645)
     UEdCached<CU> c1;
     ued_cache<CU>(c1, p);
@@ -1085,7 +1125,7 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_var_unsat(size_t n, cons
     {
       UEdCached<CU> c0;  // the neutral element (0, 1, 1, 0): (1, 1, 2, 0)
       u_set_zero(c0.ym); u_set_zero(c0.yp); u_set_zero(c0.z2); u_set_zero(c0.t2d);
-      c0.ym.v[0] = 1; c0.yp.v[0] = 1; c0.z2.v[0] = 2;
+      ued_set_small<CU, 1>(c0.ym); ued_set_small<CU, 1>(c0.yp); ued_set_small<CU, 2>(c0.z2);
       ued_row_store<CU>(row(0), c0);
     }
     // table: T[2] = 2P, T[d+1] = T[d] + P
@@ -1132,7 +1172,7 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_var_unsat(size_t n, cons
           Fe<L> cz;
           u_to_canonical<CU>(cz, pre[TBL - 1]);
           fe_inv_gcd<CS>(cz, cz);
-          inv = u_reduce(u_as<1, 3>(u_from_sat<CU>(cz)));
+          ECCX_UED_FROM_PLAIN(CU, inv, cz);
         }
 #pragma unroll
         for (int d = TBL; d >= 2; --d) {
@@ -1154,7 +1194,7 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_var_unsat(size_t n, cons
     auto booth = [&](int w, uint32_t& d, bool& neg) { booth_digit<WB, 32>(k, w, d, neg); };
     // the neutral element
     u_set_zero(q.x); u_set_zero(q.y); u_set_zero(q.z); u_set_zero(q.t);
-    q.y.v[0] = 1; q.z.v[0] = 1;
+    ued_set_small<CU, 1>(q.y); ued_set_small<CU, 1>(q.z);
     for (int win = NWIN - 1; win >= 0; --win) {
       if (win != NWIN - 1) {
         for (int j = 0; j < WB - 1; ++j) {
@@ -1175,7 +1215,7 @@ __global__ void __launch_bounds__(WG, 4) k_ed_scalarmul_var_unsat(size_t n, cons
         // select_from_table (curve25519.rs:862-869): every row read, the digit's row kept; no match = the neutral element
         U<CU, 1, 3> sym, syp, st;
         u_set_zero(sym); u_set_zero(syp); u_set_zero(st);
-        sym.v[0] = 1; syp.v[0] = 1;
+        ued_set_small<CU, 1>(sym); ued_set_small<CU, 1>(syp);
 #pragma unroll 2
         for (int j = 1; j <= TBL; ++j) {
           uint32_t w[NW];
@@ -1538,12 +1578,12 @@ __global__ void __launch_bounds__(WG) k_ed_point_add_unsat(size_t n, const uint8
   for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG) {
     auto load = [&](UEd<CU>& p, const uint8_t* __restrict__ src) {  // from_affine, curve25519.rs:638-645
       Fe<L> raw;
-      fe_load_le<CS>(raw, src);
-      p.x = u_reduce(u_as<1, 3>(u_from_sat<CU>(raw)));
-      fe_load_le<CS>(raw, src + 32);
-      p.y = u_reduce(u_as<1, 3>(u_from_sat<CU>(raw)));
+      ECCX_FE_LOAD_IO(CS, raw, src);
+      ECCX_UED_FROM_PLAIN(CU, p.x, raw);
+      ECCX_FE_LOAD_IO(CS, raw, src + 32);
+      ECCX_UED_FROM_PLAIN(CU, p.y, raw);
       u_set_zero(p.z);
-      p.z.v[0] = 1;
+      ued_set_small<CU, 1>(p.z);
       p.t = u_fit<1, 3>(u_mul(p.x, p.y));
     };
     UEd<CU> p, q, r;
@@ -1652,8 +1692,8 @@ __global__ void __launch_bounds__(WG) k_batch_to_affine_unsat(size_t n, const ui
           for (int k = 0; k < L; ++k) neutral = neutral & (ay.v[k] == (k == 0 ? 1u : 0u));
 #pragma unroll
           for (int k = 0; k < L; ++k) { ax.v[k] = rejected ? 0u : ax.v[k]; ay.v[k] = rejected ? 0u : ay.v[k]; }
-          fe_store_le<CS>(out + i * (size_t)(2 * FB), ax);
-          fe_store_le<CS>(out + i * (size_t)(2 * FB) + FB, ay);
+          ECCX_FE_STORE_IO(CS, out + i * (size_t)(2 * FB), ax);
+          ECCX_FE_STORE_IO(CS, out + i * (size_t)(2 * FB) + FB, ay);
           flags[i] = rejected ? 2 : (neutral ? 1 : 0);
         } else if constexpr (MODE == NORM_JACOBIAN_X) {
           const bool ok = present & !rejected;

@@ -185,6 +185,9 @@ struct CurveOps {
   int (*pairing_miller_grid)(int cus, size_t n);
   int (*pairing_finalexp_grid)(int cus, size_t n);
   int pairing_row_words, pairing_slab_words;
+  // 1: the C ABI refuses the options this curve has no kernel for (ECCX_TABLE_IN_LDS, ECCX_CT_GATHER, ECCX_ASSUME_SUBGROUP)
+  // with ECCX_ERR_ARG; 0 (every curve before jubjub): such options fall back to a kernel that returns the same bytes
+  int strict_opts;
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
@@ -205,6 +208,7 @@ const CurveOps& ops_P521();
 const CurveOps& ops_BLS12_381();
 const CurveOps& ops_ED25519();
 const CurveOps& ops_P256K1();
+const CurveOps& ops_JUBJUB();  // k_jubjub.hip: the Edwards templates on Fr; no LDS / gather combs, no protocol slots
 const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring slots (var, base, point_add are null)
 void h2c_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_h2c.hip: the h2c_* slots of ops_BLS12_381_G2
 void pairing_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_pairing.hip: the pairing_* slots of ops_BLS12_381_G2

@@ -11,8 +11,11 @@ from . import _lib
 # curve ids (include/eccx.h: eccx_curve)
 P256R1, P384R1, P521R1, BLS12_381_G1, ED25519, P256K1 = 0, 1, 2, 3, 4, 5
 BLS12_381_G2 = 7  # id 6 is unassigned; a G2 coordinate is an Fp2 element: field_bytes = 96 (c1 || c0), points are 192 bytes
+# id 8 is unassigned.  Jubjub: field elements and scalars 32 bytes BIG-endian, points x || y (64 bytes), the neutral
+# element (0, 1) with flag 1; wire format 32 bytes, y little-endian with x mod 2 in bit 7 of byte 31 (include/eccx.h)
+JUBJUB = 9
 CURVE_IDS = {"p256r1": P256R1, "p384r1": P384R1, "p521r1": P521R1, "bls12_381_g1": BLS12_381_G1, "ed25519": ED25519,
-             "p256k1": P256K1, "bls12_381_g2": BLS12_381_G2}
+             "p256k1": P256K1, "bls12_381_g2": BLS12_381_G2, "jubjub": JUBJUB}
 CURVE_NAMES = {v: k for k, v in CURVE_IDS.items()}
 
 VALIDATE_POINTS = 1 << 0
@@ -76,7 +79,7 @@ def scalar_bytes(curve) -> int:
 
 
 def _proj_width(cid: int) -> int:
-    return (4 if cid == ED25519 else 3) * field_bytes(cid)
+    return (4 if cid in (ED25519, JUBJUB) else 3) * field_bytes(cid)  # Edwards: X || Y || Z || T
 
 
 class Engine:
@@ -675,13 +678,15 @@ class Engine:
         return sigs
 
     def compressed_bytes(self, curve) -> int:
-        """Bytes per compressed point: FB + 1 (SEC1), 48 (zcash G1), 32 (RFC 8032)."""
+        """Bytes per compressed point: FB + 1 (SEC1), 48 (zcash G1), 32 (RFC 8032; jubjub's packed form)."""
         return self._lib.eccx_compressed_bytes(curve_id(curve))
 
     def point_decompress(self, curve, enc: bytes, *, check_subgroup: bool = False, uncompressed: bool = False):
         """Compressed encodings -> (n x 2FB affine x||y, flags): 0 point, 1 infinity encoding, 2 rejected.
         SEC1 for the sec2 curves, zcash for bls12_381_g1 (check_subgroup=True: from_compressed,
-        else from_compressed_oncurve_only), RFC 8032 for ed25519."""
+        else from_compressed_oncurve_only), RFC 8032 for ed25519.  jubjub: the packed form Zcash uses -- y little-endian,
+        bit 7 of byte 31 = x mod 2 -- decoded to big-endian x||y; rejected: y >= q, no point above y, x = 0 with the sign
+        bit set (ZIP 216)."""
         cid = curve_id(curve)
         fb = field_bytes(cid)
         eb = 2 * fb if uncompressed else self.compressed_bytes(cid)

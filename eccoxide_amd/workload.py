@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-# group orders (SEC 2 / BLS12-381 / RFC 8032; p256k1 = secp256k1, SEC 2 §2.4.1), big-endian hex
+# group orders (SEC 2 / BLS12-381 / RFC 8032 / Jubjub; p256k1 = secp256k1, SEC 2 §2.4.1), big-endian hex
 ORDERS = {
     "p256r1": "ffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551",
     "p384r1": "ffffffffffffffffffffffffffffffffffffffffffffffffc7634d81f4372ddf581a0db248b0a77aecec196accc52973",
@@ -15,6 +15,8 @@ ORDERS = {
     "ed25519": "1000000000000000000000000000000014def9dea2f79cd65812631a5cf5d3ed",
     "p256k1": "fffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141",
     "bls12_381_g2": "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001",
+    # jubjub: the 252-bit prime order r of the generator (the curve has cofactor 8; src/params/jubjub.rs ORDER_BYTES)
+    "jubjub": "0e7db4ea6533afa906673b0101343b00a6682093ccc81082d0970e5ed6f72cb7",
 }
 SEED_BASE = 0xECC051DE00000000
 

@@ -47,6 +47,9 @@
  *   - edwards25519: field elements little-endian (curve25519.rs:138); the SCALAR is the
  *     32-byte BIG-endian string the reference's loops index (Scalar::to_bytes_be,
  *     curve25519.rs:761, :842).
+ *   - jubjub: field elements AND scalars big-endian, 32 bytes (src/params/jubjub.rs, jubjub/mod.rs:165-181); points
+ *     x||y, 64 bytes; the neutral element is the ordinary point (0, 1), reported with flag 1 as for edwards25519.
+ *     See the enum comment of ECCX_JUBJUB for the wire format and the options served.
  *   - a point is its affine pair x||y, 2*FB bytes.  The Weierstrass point at infinity has
  *     no affine form (to_affine -> None, projective.rs:666-668): it is reported through
  *     the flag array with x = y = 0 bytes.
@@ -149,7 +152,29 @@ typedef enum {
    * (ECCX_PREP_BASE, ECCX_PREP_CT), eccx_reserve and the _dev / _sharded forms of these.  Everything else -- proj,
    * ECCX_MIRROR_REFERENCE, ECCX_TABLE_IN_LDS, ECCX_TABLE_IN_L2, ECCX_CT_GATHER, eccx_double_scalarmul, ECDSA -- returns
    * ECCX_ERR_ARG. */
-  ECCX_BLS12_381_G2 = 7
+  ECCX_BLS12_381_G2 = 7,
+  /* id 8 stays unassigned (an invalid curve id) */
+  /* src/curve/jubjub/mod.rs: the twisted Edwards curve -x^2 + y^2 = 1 + d x^2 y^2, d = -10240/10241, over the BLS12-381
+   * scalar field Fr (255 bits), cofactor 8, generator of the 252-bit prime order r.  A field element and a scalar are 32
+   * bytes BIG-endian (the reference's from_bytes_unchecked_be / to_bytes_be), a point record is x || y, 64 bytes:
+   * eccx_field_bytes = eccx_scalar_bytes = eccx_compressed_bytes = 32.  A scalar is used as the integer its bytes spell
+   * (any 256-bit value, not reduced modulo r); input points may be ANY point of the curve, the cofactor-8 part included
+   * (d is a non-square and -1 a square in Fr: the a = -1 addition is complete on the whole curve).  The neutral element
+   * is written as (0, 1) with flag 1, as for edwards25519; a rejected input gets flag 2 and zero bytes.
+   * Served: eccx_scalarmul_var (none, ECCX_VALIDATE_POINTS, ECCX_CT_SCAN, ECCX_MIRROR_REFERENCE / proj: n x 128 bytes
+   * X || Y || Z || T, the residues of the reference's bit-by-bit scale_bytes), eccx_scalarmul_base (none: 16-bit-window
+   * table; ECCX_TABLE_IN_L2: the reference's 64 x 15 comb; ECCX_CT_SCAN), eccx_double_scalarmul ([u1]G + [u2]Q, or
+   * [u1]G - [u2]Q with ECCX_SUBTRACT: the RedJubjub verify shape), eccx_point_add (ECCX_SUBTRACT), eccx_point_compress /
+   * _decompress, eccx_comb_table, eccx_prepare (ECCX_PREP_BASE, ECCX_PREP_CT), eccx_reserve, and the _dev / _sharded forms.
+   * Wire format (eccx_point_compress / _decompress): the packed form Zcash uses, 32 bytes: y LITTLE-endian, bit 7 of byte
+   * 31 = x mod 2.  The reference only has the pair (y, Sign).  The decoder rejects (flag 2): y >= q once the sign bit is
+   * cleared; (y^2 - 1) / (d y^2 + 1) not a square; x = 0 with the sign bit set (ZIP 216's strict rule, as our Ed25519
+   * decoder -- the reference's decompress would return x = 0).  Its square root (fixed-shape Tonelli-Shanks, 2-adicity
+   * 32) is for PUBLIC data and carries no secret-data promise; ECCX_CT_SCAN carries the same structural promise as on
+   * edwards25519 (profiles/jubjub_isa_ct.txt).
+   * Refused with ECCX_ERR_ARG: ECCX_TABLE_IN_LDS, ECCX_CT_GATHER, ECCX_CHECK_SUBGROUP (the reference has no Jubjub
+   * subgroup test either), ECCX_ASSUME_SUBGROUP, ECCX_UNCOMPRESSED, ECDSA. */
+  ECCX_JUBJUB = 9
 } eccx_curve;
 
 enum {

@@ -21,6 +21,7 @@ pub const ECCX_BLS12_381_G1: c_int = 3;
 pub const ECCX_ED25519: c_int = 4;
 pub const ECCX_P256K1: c_int = 5;
 pub const ECCX_BLS12_381_G2: c_int = 7; // 6 is unassigned
+pub const ECCX_JUBJUB: c_int = 9; // 8 is unassigned
 
 // status codes
 pub const ECCX_OK: c_int = 0;

@@ -36,6 +36,7 @@ gpu_weierstrass_curve!(p256k1, eccoxide::curve::sec2::p256k1, crate::ffi::ECCX_P
 pub mod bls12_381_g1;
 pub mod ecdsa;
 pub mod ed25519;
+pub mod jubjub;
 pub mod pairing;
 pub mod x25519;
 pub mod x448;

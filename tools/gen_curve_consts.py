@@ -7,7 +7,7 @@ math); does not import oracle/ or read /root/reference.  tests/ cross-check the
 generated values against tests/golden/params.json.  The inputs are tests/golden/bls_h2c.json and
 tests/golden/bls_h2c_g2.json: RFC 9380's constants for hashing to BLS12-381 G1 and G2 (sections
 8.8.1 and 8.8.2, appendices E.2 and E.3), checked here for what makes them the right constants
-before they are emitted.
+before they are emitted; and tests/golden/jubjub.json for Jubjub's generator.
 
     python tools/gen_curve_consts.py > eccoxide_amd/csrc/curve_consts.inc
 """
@@ -361,6 +361,68 @@ def emit_goldilocks(out):
     out.append("  static constexpr int FB = 56;")
     out.append("  static constexpr int SB = 56;")
     emit_field(out, p, L, 0, 0, plain=True)
+    out.append("};")
+
+
+JUBJUB_Q = ORDERS["BLS12_381"][0]  # the BLS12-381 scalar field Fr is Jubjub's base field
+JUBJUB_R = 0x0E7DB4EA6533AFA906673B0101343B00A6682093CCC81082D0970E5ED6F72CB7  # order of the generator (cofactor 8)
+
+
+def emit_jubjub(out):
+    """JUBJUBU / JUBJUB: the twisted Edwards curve -x^2 + y^2 = 1 + d x^2 y^2 over Fr, d = -10240/10241 (computed here),
+    the generator from tests/golden/jubjub.json, checked here for what makes them the right constants.  JUBJUBU is general
+    Montgomery on 9 x 29 bits (R = 2^261), JUBJUB its saturated twin (R = 2^256) with big-endian byte I/O.  Fr has
+    2-adicity 32: ROOT_EXP is (t - 1) / 2 for q - 1 = 2^32 t, TS_Z = 5^t the root of unity of order 2^32 the
+    Tonelli-Shanks loop of the decoder starts from."""
+    q, r = JUBJUB_Q, JUBJUB_R
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "jubjub.json")
+    with open(path) as f:
+        c = json.load(f)["params"]
+    gx, gy = int(c["gx"], 16), int(c["gy"], 16)
+    d = (-10240 * pow(10241, -1, q)) % q
+    leg = lambda v: pow(v, (q - 1) // 2, q)
+    assert all(pow(a, q - 1, q) == 1 for a in (2, 3, 5, 7, 11)) and q.bit_length() == 255
+    assert d == int(c["d"], 16) and 2 * d % q == int(c["d2"], 16) and int(c["a"], 16) == q - 1 and int(c["order"], 16) == r
+    # a = -1 is a square and d is not: the unified addition is complete on the whole curve, cofactor part included
+    assert leg(q - 1) == 1 and leg(d) == q - 1
+    # -1/d is not a square: d y^2 + 1 never vanishes, the decoder has no v == 0 case
+    assert leg((-pow(d, -1, q)) % q) == q - 1
+    assert (gy * gy - gx * gx - 1 - d * gx * gx % q * gy * gy) % q == 0, "the generator is off the curve"
+
+    def add(P, Q):
+        (x1, y1), (x2, y2) = P, Q
+        k = d * x1 * x2 * y1 * y2 % q
+        return ((x1 * y2 + y1 * x2) * pow(1 + k, -1, q) % q, (y1 * y2 + x1 * x2) * pow(1 - k, -1, q) % q)
+
+    acc = (0, 1)
+    for bit in bin(r)[2:]:
+        acc = add(acc, acc)
+        if bit == "1":
+            acc = add(acc, (gx, gy))
+    assert acc == (0, 1), "r G is not the neutral element"
+    S = 32
+    assert (q - 1) % (1 << S) == 0 and ((q - 1) >> S) & 1
+    t = (q - 1) >> S
+    z = pow(5, t, q)
+    assert leg(5) == q - 1 and pow(z, 1 << (S - 1), q) == q - 1
+    out.append("")
+    out.append("struct JUBJUB;")
+    emit_unsat(out, "JUBJUBU", "JUBJUB", q, gx, gy, 29, 9, 1, extra=(("D2", 2 * d % q), ("D", d), ("TS_Z", z)),
+               root_exp=(t - 1) // 2)
+    assert out[-1] == "" and out[-2] == "};"
+    del out[-1]
+    L = 8
+    out.append("struct JUBJUB {")
+    out.append("  static constexpr int L = 8;")
+    out.append("  static constexpr int FB = 32;")
+    out.append("  static constexpr int SB = 32;")
+    out.append("  static constexpr bool EDWARDS = true;  // a = -1 twisted Edwards, as ED25519")
+    out.append("  static constexpr bool IO_BE = true;    // field elements travel big-endian (ED25519: little-endian)")
+    out.append("  static constexpr int TS_S = %d;         // 2-adicity of q - 1" % S)
+    R = emit_field(out, q, L)
+    out.append(arr("D2", limbs(2 * d * R % q, L)))
+    out.append(arr("GX", limbs(gx * R % q, L)))
+    out.append(arr("GY", limbs(gy * R % q, L)))
     out.append("};")
 
 
@@ -729,6 +791,7 @@ def main():
     emit_bls_g2_h2c(out)
     emit_bls_pairing(out)
     emit_goldilocks(out)
+    emit_jubjub(out)
     sys.stdout.write("\n".join(out) + "\n")
 
 
