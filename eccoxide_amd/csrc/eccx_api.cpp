@@ -54,8 +54,9 @@ const CurveOps* ops_of(int curve) {
 //   B_ECDSA .. working slabs of eccx_ecdsa_verify_dev, eccx_ed25519_verify_dev, eccx_ed25519_sign_dev / _public_key_dev
 //              and eccx_ecdsa_sign_dev / _public_key_dev (the *Slab layouts below), apart from the I/O slots, which the
 //              host-buffer forms fill with their copies
+//   B_MSM      the workspace of eccx_msm_dev (kernels_msm.hpp lays it out)
 enum { IO_K = 0, IO_P = 1, IO_O = 2, IO_F = 3, IO_J = 4, IO_A = 5, IO_B = 6, NIO = 7 };
-enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, NBUF };
+enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, NBUF };
 struct DevBuf {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -527,6 +528,28 @@ int strict_err(eccx_ctx* ctx, const CurveOps* ops, uint32_t opts, uint32_t unser
   return arg_err(ctx, "jubjub: ECCX_TABLE_IN_LDS, ECCX_CT_GATHER, ECCX_CHECK_SUBGROUP and ECCX_ASSUME_SUBGROUP are not served");
 }
 
+// eccx_msm: the window width for n terms (kernels_msm.hpp: 4 .. 16 bits), a function of lg = floor(log2 n), and the
+// workspace that serves every n' <= n.  The bucket method costs about windows x (n + 2 x 2^(c-1)) additions, which alone
+// would put c near log2 n - 3; but below 2^18 terms the call is bound by the length of its serial chains, and a narrower
+// window has fewer reduction passes.  c = 2 lg - 21 inside 4 .. 16 is the fastest width the sweep of tools/bench_msm.py
+// measured at each of its sizes: 2^12 -> 4, 2^16 -> 11, 2^18 -> 15, 2^20 and 2^22 -> 16, the
+// widest key the counting sort takes.
+constexpr size_t MSM_MAX_N = (size_t)1 << 27;
+int msm_bits_of_log2(int lg) { return std::min(16, std::max(4, 2 * lg - 21)); }
+int floor_log2(size_t n) {
+  int lg = 0;
+  while (lg < 63 && ((size_t)2 << lg) <= n) ++lg;  // 0 for n <= 1
+  return lg;
+}
+int msm_window_bits(size_t n) { return msm_bits_of_log2(floor_log2(n)); }
+size_t msm_max_bytes(const CurveOps* ops, size_t n) {
+  // sizes grow with n at a fixed width; across widths the largest n' <= n of each power-of-two range decides
+  size_t bytes = 0;
+  for (int lg = 0; lg <= floor_log2(n); ++lg)
+    bytes = std::max(bytes, ops->msm_bytes(std::min(n, ((size_t)2 << lg) - 1), msm_bits_of_log2(lg)));
+  return bytes;
+}
+
 uint32_t kopts_of(uint32_t opts) { return (opts & ECCX_VALIDATE_POINTS) ? K_VALIDATE : 0u; }
 
 size_t proj_bytes(const CurveOps* ops) { return (size_t)(ops->info.edwards ? 4 : 3) * ops->info.fb; }
@@ -914,6 +937,7 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     rc = ensure_slab<EcdsaSignSlab>(ctx, B_ECSIGN, ops, max_n, nullptr);
   // eccx_pairing / eccx_pairing_check: n * max(pairs, 1) <= max_n bounds the units, the terms and the grids by max_n's
   if (!rc && (what & ECCX_PREP_PAIRING) && ops->pairing_miller) rc = ensure_pairing(ctx, need_pairing(ctx, ops, max_n, 1));
+  if (!rc && (what & ECCX_PREP_MSM) && ops->msm) rc = grow(ctx, B_MSM, msm_max_bytes(ops, max_n));
   // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
   // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
   return rc;
@@ -1556,6 +1580,74 @@ int eccx_pairing_check_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_
 int eccx_pairing_check(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
                        const uint8_t* g2_inf, uint8_t* verdicts, uint32_t opts) {
   return pairing_host(ctx, n, pairs, g1, g1_inf, g2, g2_inf, nullptr, false, verdicts, opts);
+}
+
+int eccx_msm_window_bits(size_t n) { return msm_window_bits(n); }
+
+int eccx_msm_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points, const void* d_inf, void* d_out,
+                 void* d_flag, uint32_t opts, void* stream) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (!ops->msm) return arg_err(ctx, "eccx_msm: ECCX_BLS12_381_G1 only");
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS)
+    return arg_err(ctx, "eccx_msm: opts must be 0 or ECCX_VALIDATE_POINTS (bucket addresses are scalar digits: public scalars only)");
+  if (n > MSM_MAX_N) return arg_err(ctx, "eccx_msm: more than 2^27 terms");
+  if (int rc = begin_batch(ctx, d_out && d_flag && (n == 0 || (d_scalars && d_points)))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t *out = static_cast<uint8_t*>(d_out), *flag = static_cast<uint8_t*>(d_flag);
+  if (n == 0) {  // the empty sum
+    HIP_TRY(ctx, hipMemsetAsync(out, 0, 2 * (size_t)ops->info.fb, s));
+    HIP_TRY(ctx, hipMemsetAsync(flag, ECCX_FLAG_INFINITY, 1, s));
+    return ECCX_OK;
+  }
+  // the slab holds every n below the largest seen (or reserved): the widest window does not always take the most room
+  uint8_t* ws = nullptr;
+  if (int rc = grow(ctx, B_MSM, msm_max_bytes(ops, n), &ws)) return rc;
+  uint32_t* row = nullptr;
+  HIP_TRY(ctx, ops->msm(s, ctx->cus, n, msm_window_bits(n), static_cast<const uint8_t*>(d_scalars), static_cast<const uint8_t*>(d_points),
+                        static_cast<const uint8_t*>(d_inf), ws, &row, flag, kopts_of(opts)));
+  HIP_TRY(ctx, ops->to_affine_add_u(1, s, 1, row, out, flag));
+  return ECCX_OK;
+}
+
+int eccx_msm(eccx_ctx* ctx, int curve, size_t n, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf, uint8_t* out,
+             uint8_t* flag, uint32_t opts) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (!ops->msm) return arg_err(ctx, "eccx_msm: ECCX_BLS12_381_G1 only");
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS)
+    return arg_err(ctx, "eccx_msm: opts must be 0 or ECCX_VALIDATE_POINTS (bucket addresses are scalar digits: public scalars only)");
+  if (n > MSM_MAX_N) return arg_err(ctx, "eccx_msm: more than 2^27 terms");
+  if (int rc = begin_batch(ctx, out && flag && (n == 0 || (scalars && points)))) return rc;
+  const size_t pb = 2 * (size_t)ops->info.fb;
+  // n records in, one record and one flag byte out, through the I/O slots of the other host forms
+  uint8_t *d_k = nullptr, *d_p = nullptr, *d_i = nullptr, *d_o = nullptr, *d_f = nullptr;
+  int rc = grow(ctx, B_IO + IO_O, pb, &d_o);
+  if (!rc) rc = grow(ctx, B_IO + IO_F, 1, &d_f);
+  if (!rc && n) rc = grow(ctx, B_IO + IO_K, n * (size_t)ops->info.sb, &d_k);
+  if (!rc && n) rc = grow(ctx, B_IO + IO_P, n * pb, &d_p);
+  if (!rc && n && inf) rc = grow(ctx, B_IO + IO_A, n, &d_i);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  if (n) {
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_k, scalars, n * (size_t)ops->info.sb, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_p, points, n * pb, hipMemcpyHostToDevice, s)));
+    if (inf) HIP_TRY(ctx, settled(hipMemcpyAsync(d_i, inf, n, hipMemcpyHostToDevice, s)));
+  }
+  rc = eccx_msm_dev(ctx, curve, n, d_k, d_p, d_i, d_o, d_f, opts, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  HIP_TRY(ctx, settled(hipMemcpyAsync(out, d_o, pb, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, settled(hipMemcpyAsync(flag, d_f, 1, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
 }
 
 size_t eccx_pairing_lanes(const eccx_ctx* ctx) {

@@ -188,6 +188,13 @@ struct CurveOps {
   // 1: the C ABI refuses the options this curve has no kernel for (ECCX_TABLE_IN_LDS, ECCX_CT_GATHER, ECCX_ASSUME_SUBGROUP)
   // with ECCX_ERR_ARG; 0 (every curve before jubjub): such options fall back to a kernel that returns the same bytes
   int strict_opts;
+  // Multi-scalar multiplication sum k_i P_i by the bucket method (kernels_msm.hpp; bls12_381_g1 only, else null): ONE result
+  // from n terms.  msm enqueues the whole schedule for window width c on s over a workspace of msm_bytes(n, c) bytes
+  // (256-byte aligned; sizes are functions of n and c alone, nothing is read back) and leaves a homogeneous row for
+  // to_affine_add_u at *row, inside the workspace, and 0 / 2 (a rejected term) in flag[0].  opts: OPT_VALIDATE.
+  size_t (*msm_bytes)(size_t n, int c);
+  hipError_t (*msm)(hipStream_t s, int cus, size_t n, int c, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf,
+                    uint8_t* ws, uint32_t** row, uint8_t* flag, uint32_t opts);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
@@ -211,6 +218,7 @@ const CurveOps& ops_P256K1();
 const CurveOps& ops_JUBJUB();  // k_jubjub.hip: the Edwards templates on Fr; no LDS / gather combs, no protocol slots
 const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring slots (var, base, point_add are null)
 void h2c_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_h2c.hip: the h2c_* slots of ops_BLS12_381_G2
+void msm_ops_BLS12_381(CurveOps& t);  // k_bls12_381_msm.hip: the msm slots of ops_BLS12_381
 void pairing_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_pairing.hip: the pairing_* slots of ops_BLS12_381_G2
 
 // curve25519 x-only ladder (k_ed25519.hip): rows of row_words<8>() = 24 words per unit

@@ -41,6 +41,7 @@ PREP_ECDSA_SIGN = 1024
 PREP_H2C = 2048
 PREP_PAIRING = 4096
 PREP_X448 = 8192
+PREP_MSM = 16384
 PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
@@ -156,21 +157,23 @@ class Engine:
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
-                h2c: bool = False, pairing: bool = False, x448: bool = False):
+                h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
         row buffer for 2 * max_n lanes; ecdsa_sign: the working slab of ecdsa_sign / ecdsa_public_key; h2c: the row buffer
         hash_to_g1 works in (curve "bls12_381_g1") or hash_to_g2 (curve "bls12_381_g2": two rows per unit); pairing: the
         slab and rows of pairing / pairing_check (curve "bls12_381_g2") for every shape with n * max(pairs, 1) <= max_n;
-        x448: the row buffer of x448 / x448_t (any curve: X448 has no id of its own) and, with host, its host-buffer copies."""
+        x448: the row buffer of x448 / x448_t (any curve: X448 has no id of its own) and, with host, its host-buffer copies;
+        msm: the workspace of msm / msm_t (curve "bls12_381_g1") for every n <= max_n."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
                                            | (PREP_ECDSA if ecdsa else 0) | (PREP_ED25519 if ed25519 else 0)
                                            | (PREP_ED25519_SIGN if ed25519_sign else 0)
                                            | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)
-                                           | (PREP_PAIRING if pairing else 0) | (PREP_X448 if x448 else 0)))
+                                           | (PREP_PAIRING if pairing else 0) | (PREP_X448 if x448 else 0)
+                                           | (PREP_MSM if msm else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -237,6 +240,31 @@ class Engine:
                                       (SUBTRACT if subtract else 0) | (MIRROR_REFERENCE if mirror else 0))
         self._check(rc)
         return out.raw[: n * 2 * fb], flags.raw[:n]
+
+    def msm(self, curve, scalars: bytes, points: bytes, *, inf: Optional[bytes] = None, validate: bool = False):
+        """Multi-scalar multiplication sum_i scalars[i] * points[i] by the bucket method (curve "bls12_381_g1"; PUBLIC
+        scalars only: a term is filed under its digit).  scalars: n x 32 big-endian, any 256-bit integers; points: n x 96
+        affine records, in G1 or not; inf: n flag bytes (1: the term contributes nothing, 2: rejects the result).  Returns
+        (the 96-byte record, flag): 0 a point, 1 the point at infinity, 2 rejected."""
+        cid = curve_id(curve)
+        sb, fb = scalar_bytes(cid), field_bytes(cid)
+        if len(scalars) % sb:
+            raise ValueError("scalars length is not a multiple of the scalar size")
+        n = len(scalars) // sb
+        if len(points) != n * 2 * fb:
+            raise ValueError("points length does not match the number of scalars")
+        if inf is not None and len(inf) != n:
+            raise ValueError("inf must hold one flag byte per term")
+        out = ctypes.create_string_buffer(2 * fb)
+        flag = ctypes.create_string_buffer(1)
+        rc = self._lib.eccx_msm(self._ctx, cid, n, scalars if n else None, points if n else None, inf if n else None, out, flag,
+                                VALIDATE_POINTS if validate else 0)
+        self._check(rc)
+        return out.raw, flag.raw[0]
+
+    def msm_window_bits(self, n: int) -> int:
+        """The window width msm uses for n terms (a pure function of n)."""
+        return int(self._lib.eccx_msm_window_bits(int(n)))
 
     def double_scalarmul(self, curve, u1: bytes, u2: bytes, q: bytes, *, subtract: bool = False,
                          validate: bool = False, x_only: bool = False):
@@ -801,6 +829,29 @@ class Engine:
                                           (SUBTRACT if subtract else 0) | (MIRROR_REFERENCE if mirror else 0), stream)
         self._check(rc)
         return out, flags
+
+    def msm_t(self, curve, scalars, points, out=None, flag=None, *, inf=None, validate: bool = False,
+              stream: Optional[int] = None):
+        """Device-tensor form of msm (torch.uint8 CUDA tensors): out (one 2FB-byte record) and flag (one byte) receive
+        sum_i scalars[i] * points[i]; enqueued on the stream, nothing is synchronised."""
+        import torch
+
+        cid = curve_id(curve)
+        sb, fb = scalar_bytes(cid), field_bytes(cid)
+        n = self._units(scalars, sb, "scalars")
+        if out is None:
+            out = torch.empty((2 * fb,), dtype=torch.uint8, device=scalars.device)
+        if flag is None:
+            flag = torch.empty((1,), dtype=torch.uint8, device=scalars.device)
+        self._tensors(n, ("scalars", scalars, sb), ("points", points, 2 * fb), ("inf", inf, 1))
+        self._tensors(1, ("out", out, 2 * fb), ("flag", flag, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(scalars.device).cuda_stream
+        rc = self._lib.eccx_msm_dev(self._ctx, cid, n, scalars.data_ptr() if n else None, points.data_ptr() if n else None,
+                                    inf.data_ptr() if (inf is not None and n) else None, out.data_ptr(), flag.data_ptr(),
+                                    VALIDATE_POINTS if validate else 0, stream)
+        self._check(rc)
+        return out, flag
 
     def double_scalarmul_t(self, curve, u1, u2, q, out=None, flags=None, *, subtract: bool = False,
                            validate: bool = False, x_only: bool = False, stream: Optional[int] = None):

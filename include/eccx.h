@@ -272,6 +272,9 @@ enum {
   ECCX_PREP_X448 = 1u << 13,    /* eccx_reserve (any valid curve id: X448 has none of its own): the row buffer of eccx_x448 for
                                    max_n units (192 bytes each); with ECCX_PREP_HOST the copies of the host form's scalars, u,
                                    out (56 bytes per unit each) and flags */
+  ECCX_PREP_MSM = 1u << 14,     /* eccx_reserve (bls12_381_g1): the workspace of eccx_msm for every n <= max_n (at 2^20 terms
+                                   about 0.65 GB: the converted terms, the grouped list, the partial sums and the bucket
+                                   rows); with ECCX_PREP_HOST the copies of the host form's scalars, points and flags */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -575,6 +578,37 @@ int eccx_pairing_check_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_
 /* The lanes of the pairing's largest persistent launch on this context's GPU (resident workgroups x 256): a batch of more
  * units takes the kernels' grid-stride path.  0 for a null context. */
 size_t eccx_pairing_lanes(const eccx_ctx* ctx);
+
+/* Multi-scalar multiplication: ONE result sum_i k_i * P_i from n terms, by the bucket method (Pippenger) with signed
+ * windows: what a KZG commitment, an aggregation of public keys with coefficients and batch verification by a random
+ * linear combination compute.  Every other entry point computes n results, one per lane; here the lanes cooperate.
+ *   curve   : ECCX_BLS12_381_G1 only; any other valid id is ECCX_ERR_ARG, an invalid one ECCX_ERR_CURVE
+ *   scalars : n x 32 big-endian, each used as the integer its bytes spell: any 256-bit value, NOT reduced modulo r (the
+ *             rule of the G2 and Jubjub entry points)
+ *   points  : n x 96, the affine x || y record every G1 entry point writes.  Any point of the curve is legal, in G1 or not.
+ *   inf     : NULL or n flag bytes as the other entry points write them: 1 -- the term contributes nothing, whatever its
+ *             coordinate bytes are; 2 -- a rejected operand, which rejects the result (eccx_point_add's rule)
+ *   out     : ONE 96-byte record; flag: ONE byte -- 0 a point, ECCX_FLAG_INFINITY the sum is the point at infinity
+ *             (zero bytes), ECCX_FLAG_REJECTED (zero bytes)
+ *   opts    : 0 or ECCX_VALIDATE_POINTS (a finite term with a coordinate >= p or off the curve rejects the result).
+ *             Every other bit is ECCX_ERR_ARG, returned before anything is launched or written.  That includes
+ *             ECCX_CT_SCAN: a term is filed under its digit, so bucket ADDRESSES are scalar digits and no scanning form of
+ *             this method exists -- eccx_msm is for PUBLIC scalars only.  It also includes ECCX_ASSUME_SUBGROUP: there is no
+ *             endomorphism form yet.  Without ECCX_VALIDATE_POINTS garbage input gives an unspecified result, never an
+ *             out-of-bounds access.
+ * n == 0 is the empty sum: out and flag are required and receive the point at infinity; the other pointers may be NULL.
+ * For n > 0 a null scalars, points, out or flag is ECCX_ERR_ARG; n above 2^27 is ECCX_ERR_ARG.
+ * The window width is eccx_msm_window_bits(n), a pure function of n, as is every buffer size: nothing is read back from the
+ * device.  The _dev form enqueues on `stream` and returns; after eccx_reserve(ctx, ECCX_BLS12_381_G1, max_n, ECCX_PREP_MSM)
+ * a call with n <= max_n neither allocates, frees nor synchronises.  The workspace is the context's and grow-only, and
+ * its counters are cleared on the stream by every call.  Which term lands where inside a bucket depends on the order of
+ * atomic operations, the sum does not: the same input gives the same bytes. */
+int eccx_msm(eccx_ctx* ctx, int curve, size_t n, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf, uint8_t* out,
+             uint8_t* flag, uint32_t opts);
+int eccx_msm_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points, const void* d_inf, void* d_out,
+                 void* d_flag, uint32_t opts, void* stream);
+/* The window width c (bits) eccx_msm uses for n terms: ceil(257 / c) windows of 2^(c-1) buckets.  Non-decreasing in n. */
+int eccx_msm_window_bits(size_t n);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

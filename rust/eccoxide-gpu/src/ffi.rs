@@ -64,6 +64,7 @@ pub const ECCX_PREP_ECDSA_SIGN: u32 = 1 << 10; // eccx_ecdsa_sign's / eccx_ecdsa
 pub const ECCX_PREP_H2C: u32 = 1 << 11; // eccx_hash_to_g1's / eccx_hash_to_g2's result rows
 pub const ECCX_PREP_PAIRING: u32 = 1 << 12; // eccx_pairing's / eccx_pairing_check's slab and rows
 pub const ECCX_PREP_X448: u32 = 1 << 13; // eccx_x448's result rows (any curve id) and, with ECCX_PREP_HOST, its copies
+pub const ECCX_PREP_MSM: u32 = 1 << 14; // eccx_msm's workspace for every n <= max_n (bls12_381_g1)
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -182,6 +183,13 @@ extern "C" {
                                   d_g2: *const c_void, d_g2_inf: *const c_void, d_verdicts: *mut c_void, opts: u32,
                                   stream: *mut c_void) -> c_int;
     pub fn eccx_pairing_lanes(ctx: *const eccx_ctx) -> usize;
+
+    // ONE result sum_i scalars[i] * points[i] on BLS12-381 G1, by the bucket method (public scalars only)
+    pub fn eccx_msm(ctx: *mut eccx_ctx, curve: c_int, n: usize, scalars: *const u8, points: *const u8, inf: *const u8,
+                    out: *mut u8, flag: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_msm_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_scalars: *const c_void, d_points: *const c_void,
+                        d_inf: *const c_void, d_out: *mut c_void, d_flag: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_msm_window_bits(n: usize) -> c_int;
 
     // X25519 over a batch                                    protocol::x25519::x25519
     pub fn eccx_x25519(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,

@@ -37,6 +37,7 @@ pub mod bls12_381_g1;
 pub mod ecdsa;
 pub mod ed25519;
 pub mod jubjub;
+pub mod msm;
 pub mod pairing;
 pub mod x25519;
 pub mod x448;
