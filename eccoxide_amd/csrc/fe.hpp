@@ -19,6 +19,24 @@
 // v_addc_co_u32 into a third word.  Montgomery reduction is interleaved in the
 // same column chain (FIPS form), and limbs of the modulus that are zero are
 // skipped at compile time (P-256: 3 of 8, P-384: 2 of 12).
+//
+// Contract (pinned one operation at a time by tests/test_sat_layer_gpu.py through tests/hip_sat; R = 2^(32 L)):
+//   * Operands are canonical, i.e. below p, and so is every result.  fe_add, fe_sub, fe_neg, fe_mul, fe_sqr, fe_mul_k,
+//     fe_from_mont and inv_gcd.hpp's fe_inv_fast promise nothing for an operand at or above p.
+//   * The exceptions take any value a load can produce (8 FB bits): fe_to_mont, whose result is the canonical working
+//     form of the value mod p, fe_is_canonical, fe_is_zero, fe_eq, and the byte I/O (fe_load_* check no range).
+//   * Each product ends in ONE cond_sub_p, which is enough because the value entering it is below 2p:
+//       Montgomery (fe_mul_impl)   t = (a b + m p) / R with m < R: a, b < p give t < (p^2 + R p) / R < 2p; fe_to_mont's
+//                                  raw < R with R2 < p gives the same bound.  Where 2p > R (P256, P384, P256K1) t may
+//                                  reach R: the carry word handed to cond_sub_p decides then, the borrow alone below R.
+//       2^255 - 19 (fe_mul_pm19)   a, b < 2^256: the carry word of lo + 38 hi is at most 38, so top <= 77 and
+//                                  u < 2^255 + 19 * 80 < 2p.  fe_to_mont (b = 1) has top <= 1: u <= 2^255 + 18.
+//       Mersenne (fe_mul_mersenne) a b < 2^K p (canonical operands; any raw < R times 1): the first fold is below 2p, the
+//                                  second leaves s <= p, with s = p only for a non-zero multiple of p, which canonical
+//                                  operands cannot produce; fe_to_mont(k p) does (a P-521 coordinate of 66 bytes
+//                                  holds k p for k up to 127).
+//   * CURVE448 has R2 = ONE = 1 over Montgomery-shaped N0 and PP1: its product, conversions and fe_inv_fast are
+//     meaningless and nothing instantiates them; its add, sub, neg, predicates and byte I/O are in use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
