@@ -66,6 +66,17 @@ SYMBOLS = {
     "eccx_msm": (c_int, [c_void_p, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_msm_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_msm_window_bits": (c_int, [c_size_t]),
+    "eccx_point_sum": (c_int, [c_void_p, c_int, c_size_t, _u8p, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_point_sum_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_bls_public_key": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_bls_public_key_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_bls_sign": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_bls_sign_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_bls_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_bls_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_bls_fast_aggregate_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, c_uint32]),
+    "eccx_bls_fast_aggregate_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                   c_size_t, c_void_p, c_uint32, c_void_p]),
     "eccx_comb_table": (c_int, [c_void_p, c_int, _u8p]),
     "eccx_scalarmul_var_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_scalarmul_base_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, c_uint32]),

@@ -55,8 +55,9 @@ const CurveOps* ops_of(int curve) {
 //              and eccx_ecdsa_sign_dev / _public_key_dev (the *Slab layouts below), apart from the I/O slots, which the
 //              host-buffer forms fill with their copies
 //   B_MSM      the workspace of eccx_msm_dev (kernels_msm.hpp lays it out)
+//   B_BLS      the working slab of the eccx_bls_* entry points (BlsSlab below)
 enum { IO_K = 0, IO_P = 1, IO_O = 2, IO_F = 3, IO_J = 4, IO_A = 5, IO_B = 6, NIO = 7 };
-enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, NBUF };
+enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, NBUF };
 struct DevBuf {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -262,6 +263,17 @@ struct EdSignSlab {
 struct EcdsaSignSlab {
   uint8_t *pts, *lflags;
   static EcdsaSignSlab lay(Carve& c, const CurveOps* ops, size_t n) { return {c.take(n * 2 * (size_t)ops->info.fb), c.take(n)}; }
+};
+// BLS signatures, n = max(units, keys of FastAggregateVerify), every record at the wider group's size so that one layout
+// serves both variants: the sanitised secrets (n x 32); the decoded or derived key and signature (n x 192 each) and H(m)
+// (n x 192) with their flags; the decoded keys of the groups (n x 192) with theirs; the pairing's unit-major terms, pairs =
+// 2 (g1 n x 192, g2 n x 384) with their infinity flags (2n each); the pairing's verdicts (n)
+struct BlsSlab {
+  uint8_t *sk, *key, *key_fl, *sig, *sig_fl, *h, *h_fl, *keys, *keys_fl, *g1, *g2, *g1_inf, *g2_inf, *pv;
+  static BlsSlab lay(Carve& c, const CurveOps*, size_t n) {
+    return {c.take(n * 32), c.take(n * 192), c.take(n), c.take(n * 192), c.take(n), c.take(n * 192), c.take(n),
+            c.take(n * 192), c.take(n), c.take(n * 192), c.take(n * 384), c.take(2 * n), c.take(2 * n), c.take(n)};
+  }
 };
 // out == nullptr: only size the slab (eccx_reserve)
 template <class Slab>
@@ -938,6 +950,15 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
   // eccx_pairing / eccx_pairing_check: n * max(pairs, 1) <= max_n bounds the units, the terms and the grids by max_n's
   if (!rc && (what & ECCX_PREP_PAIRING) && ops->pairing_miller) rc = ensure_pairing(ctx, need_pairing(ctx, ops, max_n, 1));
   if (!rc && (what & ECCX_PREP_MSM) && ops->msm) rc = grow(ctx, B_MSM, msm_max_bytes(ops, max_n));
+  // eccx_bls_*: the slab, and with it what the hash (two rows per unit on G2), the pairing (pairs = 2), the group sum, the
+  // decoders and both secret-scalar ladders and combs' rows need, on both curves
+  if (!rc && (what & ECCX_PREP_BLS)) {
+    rc = ensure_slab<BlsSlab>(ctx, B_BLS, ops, max_n, nullptr);
+    const CurveOps *g1 = ops_of(ECCX_BLS12_381_G1), *g2 = ops_of(ECCX_BLS12_381_G2);
+    if (!rc) rc = ensure_work(ctx, g2, 2 * max_n, {need_var_ct(ctx, g2, max_n, false)});
+    if (!rc) rc = ensure_work(ctx, g1, max_n, {need_var_ct(ctx, g1, max_n, false), need_var_ct(ctx, g1, max_n, true), need_var_fixup(ctx, g1, max_n)});
+    if (!rc) rc = ensure_pairing(ctx, need_pairing(ctx, g2, max_n, 2));
+  }
   // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
   // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
   return rc;
@@ -1648,6 +1669,285 @@ int eccx_msm(eccx_ctx* ctx, int curve, size_t n, const uint8_t* scalars, const u
   HIP_TRY(ctx, settled(hipMemcpyAsync(flag, d_f, 1, hipMemcpyDeviceToHost, s)));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return ECCX_OK;
+}
+
+namespace {
+// eccx_point_sum[_dev]: everything checkable before a device is touched
+int point_sum_args(eccx_ctx* ctx, const CurveOps* ops, uint32_t opts) {
+  if (!ops->point_sum) return arg_err(ctx, "eccx_point_sum: ECCX_BLS12_381_G1 and ECCX_BLS12_381_G2 only");
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS) return arg_err(ctx, "eccx_point_sum: opts must be 0 or ECCX_VALIDATE_POINTS");
+  return ECCX_OK;
+}
+}  // namespace
+
+int eccx_point_sum_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_offsets, size_t members, const void* d_points, const void* d_inf,
+                       void* d_out, void* d_flags, uint32_t opts, void* stream) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = point_sum_args(ctx, ops, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_offsets && d_out && d_flags && (members == 0 || d_points))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t* flags = static_cast<uint8_t*>(d_flags);
+  // one homogeneous row per group, then the group law's normalisation
+  if (int rc = ensure_rows(ctx, ops, n)) return rc;
+  HIP_TRY(ctx, ops->point_sum(s, ctx->cus, n, members, static_cast<const uint64_t*>(d_offsets), static_cast<const uint8_t*>(d_points),
+                              static_cast<const uint8_t*>(d_inf), ctx->rows(), flags, kopts_of(opts)));
+  HIP_TRY(ctx, ops->to_affine_add_u(norm_grid(ctx, n), s, n, ctx->rows(), static_cast<uint8_t*>(d_out), flags));
+  return ECCX_OK;
+}
+
+int eccx_point_sum(eccx_ctx* ctx, int curve, size_t n, const uint64_t* offsets, size_t members, const uint8_t* points, const uint8_t* inf,
+                   uint8_t* out, uint8_t* flags, uint32_t opts) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = point_sum_args(ctx, ops, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (!offsets || !out || !flags || (members && !points)) return arg_err(ctx, "null buffer");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return arg_err(ctx, "eccx_point_sum: the offsets decrease");
+  if (offsets[n] - offsets[0] > members) return arg_err(ctx, "eccx_point_sum: the last offset lies beyond the members");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t pb = 2 * (size_t)ops->info.fb;
+  // n + 1 offsets and `members` records in, n records and flag bytes out, through the I/O slots of the other host forms
+  uint8_t *d_off = nullptr, *d_p = nullptr, *d_i = nullptr, *d_o = nullptr, *d_f = nullptr;
+  int rc = grow(ctx, B_IO + IO_K, (n + 1) * sizeof(uint64_t), &d_off);
+  if (!rc) rc = grow(ctx, B_IO + IO_O, n * pb, &d_o);
+  if (!rc) rc = grow(ctx, B_IO + IO_F, n, &d_f);
+  if (!rc && members) rc = grow(ctx, B_IO + IO_P, members * pb, &d_p);
+  if (!rc && members && inf) rc = grow(ctx, B_IO + IO_A, members, &d_i);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  HIP_TRY(ctx, settled(hipMemcpyAsync(d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s)));
+  if (members) {
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_p, points, members * pb, hipMemcpyHostToDevice, s)));
+    if (inf) HIP_TRY(ctx, settled(hipMemcpyAsync(d_i, inf, members, hipMemcpyHostToDevice, s)));
+  }
+  rc = eccx_point_sum_dev(ctx, curve, n, d_off, members, d_p, d_i, d_o, d_f, opts, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  HIP_TRY(ctx, settled(hipMemcpyAsync(out, d_o, n * pb, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, settled(hipMemcpyAsync(flags, d_f, n, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
+}
+
+namespace {
+// The four eccx_bls_* entry points are one body each for both variants: the struct names the two curves, as H2cWhat does.
+struct BlsWhat {
+  int min_sig, key_curve, sig_curve;
+  const H2cWhat* h2c;  // H(m) lands in the signatures' group
+  size_t key_enc, sig_enc, key_pb, sig_pb;
+};
+const BlsWhat BLS_MIN_PK = {0, ECCX_BLS12_381_G1, ECCX_BLS12_381_G2, &H2C_G2, 48, 96, 96, 192};
+const BlsWhat BLS_MIN_SIG_W = {1, ECCX_BLS12_381_G2, ECCX_BLS12_381_G1, &H2C_G1, 96, 48, 192, 96};
+const BlsWhat* bls_what(uint32_t opts) { return (opts & ECCX_BLS_MIN_SIG) ? &BLS_MIN_SIG_W : &BLS_MIN_PK; }
+// opts: ECCX_BLS_MIN_SIG; the secret-scalar entry points also take ECCX_CT_GATHER for min-pk (the G1 comb has the gather form)
+int bls_opts(eccx_ctx* ctx, uint32_t opts, bool secret, const char* msg) {
+  uint32_t allowed = ECCX_BLS_MIN_SIG;
+  if (secret && !(opts & ECCX_BLS_MIN_SIG)) allowed |= ECCX_CT_GATHER;
+  return (opts & ~allowed) ? arg_err(ctx, msg) : ECCX_OK;
+}
+const char* const BLS_VERIFY_OPTS = "eccx_bls_verify: opts must be 0 or ECCX_BLS_MIN_SIG";
+const char* const BLS_SECRET_OPTS = "eccx_bls_sign / eccx_bls_public_key: opts must be 0, ECCX_BLS_MIN_SIG, or ECCX_CT_GATHER (min-pk only)";
+
+// an error between the range kernel and the finishing kernel: the slab's copy of the secrets does not outlive the call
+// either (enqueued behind whatever was launched; the error that brought us here comes first)
+int bls_wipe_secrets(eccx_ctx* ctx, int rc, const BlsSlab& b, size_t n, hipStream_t s) {
+  (void)ctx;
+  (void)hipMemsetAsync(b.sk, 0, n * 32, s);
+  return rc;
+}
+
+int bls_public_key_dev(eccx_ctx* ctx, size_t n, const void* d_secrets, void* d_pubkeys, void* d_status, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, true, BLS_SECRET_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_secrets && d_pubkeys && d_status)) return rc;
+  const BlsWhat& w = *bls_what(opts);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BlsSlab b;
+  if (int rc = ensure_slab(ctx, B_BLS, nullptr, n, &b)) return rc;
+  uint8_t* status = static_cast<uint8_t*>(d_status);
+  // the range test by selects, the secret-scalar comb, the normalisation (inside it), the compressor, the zeroing
+  HIP_TRY(ctx, eccx::launch_bls_secret_prepare(s, n, static_cast<const uint8_t*>(d_secrets), b.sk, status));
+  int rc = eccx_scalarmul_base_dev(ctx, w.key_curve, n, b.sk, b.key, b.key_fl, nullptr, ECCX_CT_SCAN | (opts & ECCX_CT_GATHER), s);
+  if (!rc) rc = eccx_point_compress_dev(ctx, w.key_curve, n, b.key, b.key_fl, d_pubkeys, 0, s);
+  if (rc) return bls_wipe_secrets(ctx, rc, b, n, s);
+  const hipError_t e = eccx::launch_bls_secret_finish(s, n, nullptr, status, static_cast<uint8_t*>(d_pubkeys), (int)w.key_enc, b.sk);
+  if (e != hipSuccess) (void)bls_wipe_secrets(ctx, ECCX_ERR_HIP, b, n, s);
+  HIP_TRY(ctx, e);
+  return ECCX_OK;
+}
+
+int bls_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                 const void* d_secrets, void* d_sigs, void* d_status, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, true, BLS_SECRET_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_msgs && d_offsets && d_secrets && d_sigs && d_status && (dst || dst_len == 0))) return rc;
+  const BlsWhat& w = *bls_what(opts);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BlsSlab b;
+  if (int rc = ensure_slab(ctx, B_BLS, nullptr, n, &b)) return rc;
+  uint8_t* status = static_cast<uint8_t*>(d_status);
+  HIP_TRY(ctx, eccx::launch_bls_secret_prepare(s, n, static_cast<const uint8_t*>(d_secrets), b.sk, status));
+  // H(m) into the slab (the hash works in the context's rows, which the ladder behind reuses), then sk * H(m) on the
+  // secret-scalar ladder: H(m) is in the subgroup, which the G1 ladder is told
+  int rc = hash_to_curve_dev(ctx, *w.h2c, n, d_msgs, d_offsets, dst, dst_len, b.h, b.h_fl, 0, s);
+  // (ECCX_CT_GATHER, accepted for min-pk, is the comb's lookup: the ladders have no gather form and it changes nothing here)
+  const uint32_t lopts = ECCX_CT_SCAN | (w.min_sig ? (uint32_t)ECCX_ASSUME_SUBGROUP : 0u);
+  if (!rc) rc = eccx_scalarmul_var_dev(ctx, w.sig_curve, n, b.sk, b.h, b.sig, b.sig_fl, nullptr, lopts, s);
+  if (!rc) rc = eccx_point_compress_dev(ctx, w.sig_curve, n, b.sig, b.sig_fl, d_sigs, 0, s);
+  if (rc) return bls_wipe_secrets(ctx, rc, b, n, s);
+  const hipError_t e = eccx::launch_bls_secret_finish(s, n, b.h_fl, status, static_cast<uint8_t*>(d_sigs), (int)w.sig_enc, b.sk);
+  if (e != hipSuccess) (void)bls_wipe_secrets(ctx, ECCX_ERR_HIP, b, n, s);
+  HIP_TRY(ctx, e);
+  return ECCX_OK;
+}
+
+// eccx_bls_verify_dev (d_key_offsets == null: one key per unit) and eccx_bls_fast_aggregate_verify_dev
+int bls_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                   const void* d_sigs, const void* d_pubkeys, bool aggregate, const void* d_key_offsets, size_t keys, void* d_verdicts,
+                   uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_VERIFY_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_msgs && d_offsets && d_sigs && d_verdicts && (dst || dst_len == 0) &&
+                                    (aggregate ? (d_key_offsets && (keys == 0 || d_pubkeys)) : d_pubkeys != nullptr)))
+    return rc;
+  const BlsWhat& w = *bls_what(opts);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BlsSlab b;
+  if (int rc = ensure_slab(ctx, B_BLS, nullptr, std::max(n, aggregate ? keys : (size_t)0), &b)) return rc;
+  uint8_t* verdicts = static_cast<uint8_t*>(d_verdicts);
+  // both decoders with their in-place subgroup tests
+  if (aggregate) {
+    // every key through KeyValidate (the identity is no key), then one sum per unit's group
+    if (keys) {
+      if (int rc = eccx_point_decompress_dev(ctx, w.key_curve, keys, d_pubkeys, b.keys, b.keys_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+      HIP_TRY(ctx, eccx::launch_bls_key_flags(s, keys, b.keys_fl));
+    }
+    if (int rc = eccx_point_sum_dev(ctx, w.key_curve, n, d_key_offsets, keys, b.keys, b.keys_fl, b.key, b.key_fl, 0, s)) return rc;
+  } else {
+    if (int rc = eccx_point_decompress_dev(ctx, w.key_curve, n, d_pubkeys, b.key, b.key_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+  }
+  if (int rc = eccx_point_decompress_dev(ctx, w.sig_curve, n, d_sigs, b.sig, b.sig_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+  // the hash's output lands in the slab before the pairing reuses the rows it worked in (one stream: ordered)
+  if (int rc = hash_to_curve_dev(ctx, *w.h2c, n, d_msgs, d_offsets, dst, dst_len, b.h, b.h_fl, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_bls_assemble(s, n, w.min_sig, b.key, b.key_fl, b.sig, b.sig_fl, b.h, b.h_fl,
+                                         aggregate ? static_cast<const uint64_t*>(d_key_offsets) : nullptr, keys, b.g1, b.g1_inf, b.g2,
+                                         b.g2_inf, verdicts));
+  if (int rc = pairing_dev(ctx, n, 2, b.g1, b.g1_inf, b.g2, b.g2_inf, nullptr, false, b.pv, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_bls_fold(s, n, b.pv, verdicts));
+  return ECCX_OK;
+}
+
+// the host forms: messages as eccx_hash_to_g2 takes them, one chunk (the kernels dwarf the copies)
+int bls_msgs_host(eccx_ctx* ctx, size_t n, EdMsgs& m, const uint8_t* dst, size_t dst_len, bool others_ok, const char* decrease) {
+  if (!m.offsets || !others_ok || (!dst && dst_len != 0)) return arg_err(ctx, "null buffer");
+  if (int rc = m.check(ctx, n, decrease)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return m.grow_slots(ctx, n);
+}
+}  // namespace
+
+int eccx_bls_public_key_dev(eccx_ctx* ctx, size_t n, const void* d_secrets, void* d_pubkeys, void* d_status, uint32_t opts, void* stream) {
+  return bls_public_key_dev(ctx, n, d_secrets, d_pubkeys, d_status, opts, stream);
+}
+int eccx_bls_public_key(eccx_ctx* ctx, size_t n, const uint8_t* secrets, uint8_t* pubkeys, uint8_t* status, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, true, BLS_SECRET_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, secrets && pubkeys && status)) return rc;
+  HostBuf bufs[] = {in_buf(IO_P, secrets, 32), out_buf(IO_O, pubkeys, bls_what(opts)->key_enc), out_buf(IO_F, status, 1)};
+  const int rc = host_pipeline(ctx, n, bufs, /*chunked=*/false, [&](size_t, size_t cnt, uint8_t* const* d) {
+    return bls_public_key_dev(ctx, cnt, d[0], d[1], d[2], opts, ctx->stream);
+  });
+  return wipe_io(ctx, rc, bufs[0], nullptr, n);
+}
+int eccx_bls_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                      const void* d_secrets, void* d_sigs, void* d_status, uint32_t opts, void* stream) {
+  return bls_sign_dev(ctx, n, d_msgs, d_offsets, dst, dst_len, d_secrets, d_sigs, d_status, opts, stream);
+}
+int eccx_bls_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                  const uint8_t* secrets, uint8_t* sigs, uint8_t* status, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, true, BLS_SECRET_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  EdMsgs m{msgs, offsets};
+  if (int rc = bls_msgs_host(ctx, n, m, dst, dst_len, secrets && sigs && status, "eccx_bls_sign: the offsets decrease")) return rc;
+  HostBuf bufs[] = {in_buf(IO_P, secrets, 32), out_buf(IO_O, sigs, bls_what(opts)->sig_enc), out_buf(IO_F, status, 1)};
+  const int rc = host_pipeline(
+      ctx, n, bufs, /*chunked=*/false,
+      [&](size_t lo, size_t cnt, uint8_t* const* d) {
+        return bls_sign_dev(ctx, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d[1], d[2], opts, ctx->stream);
+      },
+      [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
+  return wipe_io(ctx, rc, bufs[0], nullptr, n);
+}
+int eccx_bls_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        const void* d_sigs, const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream) {
+  return bls_verify_dev(ctx, n, d_msgs, d_offsets, dst, dst_len, d_sigs, d_pubkeys, false, nullptr, 0, d_verdicts, opts, stream);
+}
+int eccx_bls_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    const uint8_t* sigs, const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_VERIFY_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  EdMsgs m{msgs, offsets};
+  if (int rc = bls_msgs_host(ctx, n, m, dst, dst_len, sigs && pubkeys && verdicts, "eccx_bls_verify: the offsets decrease")) return rc;
+  const BlsWhat& w = *bls_what(opts);
+  HostBuf bufs[] = {in_buf(IO_P, sigs, w.sig_enc), in_buf(IO_A, pubkeys, w.key_enc), out_buf(IO_F, verdicts, 1)};
+  return host_pipeline(
+      ctx, n, bufs, /*chunked=*/false,
+      [&](size_t lo, size_t cnt, uint8_t* const* d) {
+        return bls_verify_dev(ctx, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d[1], false, nullptr, 0, d[2], opts, ctx->stream);
+      },
+      [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
+}
+int eccx_bls_fast_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
+                                       size_t dst_len, const void* d_sigs, const void* d_pubkeys, const void* d_key_offsets, size_t keys,
+                                       void* d_verdicts, uint32_t opts, void* stream) {
+  return bls_verify_dev(ctx, n, d_msgs, d_offsets, dst, dst_len, d_sigs, d_pubkeys, true, d_key_offsets, keys, d_verdicts, opts, stream);
+}
+int eccx_bls_fast_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                                   size_t dst_len, const uint8_t* sigs, const uint8_t* pubkeys, const uint64_t* key_offsets, size_t keys,
+                                   uint8_t* verdicts, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_VERIFY_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  EdMsgs m{msgs, offsets};
+  if (int rc = bls_msgs_host(ctx, n, m, dst, dst_len, sigs && key_offsets && (keys == 0 || pubkeys) && verdicts,
+                             "eccx_bls_fast_aggregate_verify: the offsets decrease"))
+    return rc;
+  const BlsWhat& w = *bls_what(opts);
+  // the key offsets and the flat key array are no per-unit records: copied whole, ahead of the one chunk, on its stream
+  uint8_t *d_ko = nullptr, *d_keys = nullptr;
+  int rc = grow(ctx, B_IO + IO_A, (n + 1) * sizeof(uint64_t), &d_ko);
+  if (!rc && keys) rc = grow(ctx, B_IO + IO_B, keys * w.key_enc, &d_keys);
+  if (rc) return rc;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(ctx->stream);
+    return e;
+  };
+  HIP_TRY(ctx, settled(hipMemcpyAsync(d_ko, key_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream)));
+  if (keys) HIP_TRY(ctx, settled(hipMemcpyAsync(d_keys, pubkeys, keys * w.key_enc, hipMemcpyHostToDevice, ctx->stream)));
+  HostBuf bufs[] = {in_buf(IO_P, sigs, w.sig_enc), out_buf(IO_F, verdicts, 1)};
+  return host_pipeline(
+      ctx, n, bufs, /*chunked=*/false,
+      [&](size_t lo, size_t cnt, uint8_t* const* d) {
+        return bls_verify_dev(ctx, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d_keys, true, d_ko, keys, d[1], opts, ctx->stream);
+      },
+      [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
 }
 
 size_t eccx_pairing_lanes(const eccx_ctx* ctx) {

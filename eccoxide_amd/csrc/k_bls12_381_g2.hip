@@ -102,6 +102,7 @@ const CurveOps& ops_BLS12_381_G2() {
     t.base_unsat = base_index_;
     h2c_ops_BLS12_381_G2(t);  // hashing to G2
     pairing_ops_BLS12_381_G2(t);  // the pairing
+    point_sum_ops_BLS12_381_G2(t);  // sums of ragged groups
     return t;
   }();
   return o;

@@ -195,6 +195,13 @@ struct CurveOps {
   size_t (*msm_bytes)(size_t n, int c);
   hipError_t (*msm)(hipStream_t s, int cus, size_t n, int c, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf,
                     uint8_t* ws, uint32_t** row, uint8_t* flag, uint32_t opts);
+  // Sums of ragged groups of points (kernels_bls_sig.hpp; bls12_381_g1 and bls12_381_g2, else null): ONE result per group.
+  // Group g is members offsets[g] - offsets[0] .. offsets[g + 1] - offsets[0] of `members` affine records with optional
+  // flags (1: contributes nothing; 2: rejects its group).  Leaves n homogeneous rows for to_affine_add_u and 0 / 2 in flags (a
+  // rejected member, or a range that decreases or leaves the records: such a group reads nothing).  Picks its own grid;
+  // nothing is read back.  opts: OPT_VALIDATE.
+  hipError_t (*point_sum)(hipStream_t s, int cus, size_t n, size_t members, const uint64_t* offsets, const uint8_t* points,
+                          const uint8_t* inf, uint32_t* rows, uint8_t* flags, uint32_t opts);
 };
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
@@ -220,6 +227,8 @@ const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring s
 void h2c_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_h2c.hip: the h2c_* slots of ops_BLS12_381_G2
 void msm_ops_BLS12_381(CurveOps& t);  // k_bls12_381_msm.hip: the msm slots of ops_BLS12_381
 void pairing_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_pairing.hip: the pairing_* slots of ops_BLS12_381_G2
+void point_sum_ops_BLS12_381(CurveOps& t);     // k_bls12_381_sig.hip: the point_sum slot of ops_BLS12_381 ...
+void point_sum_ops_BLS12_381_G2(CurveOps& t);  // ... and of ops_BLS12_381_G2
 
 // curve25519 x-only ladder (k_ed25519.hip): rows of row_words<8>() = 24 words per unit
 hipError_t launch_x25519_ladder(int grid, hipStream_t s, size_t n, const uint8_t* scalars, const uint8_t* u,
@@ -234,6 +243,17 @@ hipError_t launch_x448_to_u(int grid, hipStream_t s, size_t n, const uint32_t* r
 int x448_ladder_grid(int cus, size_t n);
 int x448_row_words();
 int x448_norm_units();
+
+// the byte-moving kernels of the BLS signature scheme (kernels_bls_sig.hpp, k_bls12_381_sig.hip): the range test of the
+// secrets with its select, the zeroing behind the compressor, KeyValidate on the decoders' flags, the pairing's term
+// buffers with the pre-verdicts, and the last fold onto ECCX_SIG_*
+hipError_t launch_bls_secret_prepare(hipStream_t s, size_t n, const uint8_t* secrets, uint8_t* sk, uint8_t* status);
+hipError_t launch_bls_secret_finish(hipStream_t s, size_t n, const uint8_t* hflags, uint8_t* status, uint8_t* out, int width, uint8_t* sk);
+hipError_t launch_bls_key_flags(hipStream_t s, size_t n, uint8_t* flags);
+hipError_t launch_bls_assemble(hipStream_t s, size_t n, int min_sig, const uint8_t* key_xy, const uint8_t* key_fl, const uint8_t* sig_xy,
+                               const uint8_t* sig_fl, const uint8_t* h_xy, const uint8_t* h_fl, const uint64_t* key_offsets, size_t keys,
+                               uint8_t* g1, uint8_t* g1_inf, uint8_t* g2, uint8_t* g2_inf, uint8_t* verdicts);
+hipError_t launch_bls_fold(hipStream_t s, size_t n, const uint8_t* pairing_verdicts, uint8_t* verdicts);
 
 constexpr int LAUNCH_WG = 256;
 

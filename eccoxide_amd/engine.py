@@ -33,6 +33,7 @@ CT_GATHER = 1 << 10
 OUT_X_ONLY = 1 << 11
 PUBKEY_SEC1 = 1 << 12
 H2C_NU = 1 << 13
+BLS_MIN_SIG = 1 << 14
 PREP_VAR, PREP_BASE, PREP_BASE_LDS, PREP_MIRROR, PREP_CT, PREP_CT_GATHER, PREP_HOST = 1, 2, 4, 8, 16, 32, 64
 PREP_ECDSA = 128
 PREP_ED25519 = 256
@@ -42,6 +43,7 @@ PREP_H2C = 2048
 PREP_PAIRING = 4096
 PREP_X448 = 8192
 PREP_MSM = 16384
+PREP_BLS = 32768
 PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
@@ -49,6 +51,16 @@ SIG_INVALID, SIG_VALID, SIG_MALFORMED, SIG_BAD_KEY = 0, 1, 2, 3
 # status bytes of ecdsa_sign / ecdsa_public_key (include/eccx.h: ECCX_SIGN_*)
 SIGN_NONE, SIGN_OK = 0, 1
 ECDSA_CURVES = (P256R1, P384R1, P521R1, P256K1)
+# the standard tags of BLS signatures (draft-irtf-cfrg-bls-signature section 4.2): basic, message augmentation, proof of
+# possession, and the tag PopProve / PopVerify sign the key's own bytes under; min-pk (signatures in G2), then min-sig
+BLS_DST_NUL = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_"
+BLS_DST_AUG = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_AUG_"
+BLS_DST_POP = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"
+BLS_DST_POP_PROOF = b"BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"
+BLS_DST_NUL_MIN_SIG = b"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_"
+BLS_DST_AUG_MIN_SIG = b"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_AUG_"
+BLS_DST_POP_MIN_SIG = b"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_POP_"
+BLS_DST_POP_PROOF_MIN_SIG = b"BLS_POP_BLS12381G1_XMD:SHA-256_SSWU_RO_POP_"
 
 
 class EccxError(RuntimeError):
@@ -157,7 +169,7 @@ class Engine:
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
-                h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False):
+                h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False, bls: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
@@ -165,7 +177,8 @@ class Engine:
         hash_to_g1 works in (curve "bls12_381_g1") or hash_to_g2 (curve "bls12_381_g2": two rows per unit); pairing: the
         slab and rows of pairing / pairing_check (curve "bls12_381_g2") for every shape with n * max(pairs, 1) <= max_n;
         x448: the row buffer of x448 / x448_t (any curve: X448 has no id of its own) and, with host, its host-buffer copies;
-        msm: the workspace of msm / msm_t (curve "bls12_381_g1") for every n <= max_n."""
+        msm: the workspace of msm / msm_t (curve "bls12_381_g1") for every n <= max_n; bls: the slab of the bls_* calls
+        (curve "bls12_381_g2") and what their parts need on both curves, for max(n, keys) <= max_n."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
@@ -173,7 +186,7 @@ class Engine:
                                            | (PREP_ED25519_SIGN if ed25519_sign else 0)
                                            | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)
                                            | (PREP_PAIRING if pairing else 0) | (PREP_X448 if x448 else 0)
-                                           | (PREP_MSM if msm else 0)))
+                                           | (PREP_MSM if msm else 0) | (PREP_BLS if bls else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -261,6 +274,229 @@ class Engine:
                                 VALIDATE_POINTS if validate else 0)
         self._check(rc)
         return out.raw, flag.raw[0]
+
+    def point_sum(self, curve, points: bytes, offsets, *, inf: Optional[bytes] = None, validate: bool = False):
+        """One sum per ragged group of points (eccx_point_sum; curves "bls12_381_g1" and "bls12_381_g2"): group g is the
+        records offsets[g] - offsets[0] .. offsets[g + 1] - offsets[0] of `points` (affine x || y records, in the
+        prime-order subgroup or not); offsets holds n + 1 non-decreasing integers.  inf: one flag byte per record (1: the
+        member contributes nothing, 2: rejects its group).  Returns (n records, n flags): 0 a point, 1 the sum is the point
+        at infinity (the empty group included), 2 rejected."""
+        import numpy as np
+
+        cid = curve_id(curve)
+        pb = 2 * field_bytes(cid)
+        if len(points) % pb:
+            raise ValueError(f"points must be members x {pb} bytes")
+        members = len(points) // pb
+        if inf is not None and len(inf) != members:
+            raise ValueError("inf must hold one flag byte per member")
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offs.ndim != 1 or offs.size < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        n = offs.size - 1
+        out = ctypes.create_string_buffer(max(1, n * pb))
+        flags = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.eccx_point_sum(self._ctx, cid, n, offs.ctypes.data, members, points if members else None,
+                                      inf if members else None, out, flags, VALIDATE_POINTS if validate else 0)
+        self._check(rc)
+        return out.raw[: n * pb], flags.raw[:n]
+
+    def bls_aggregate(self, encodings: bytes, groups, *, curve="bls12_381_g2", check_subgroup: bool = False):
+        """Aggregate BLS signatures (or public keys) group by group: decompress, one sum per group, compress -- three calls
+        of this engine.  encodings: the zcash-compressed points of all groups, back to back (96-byte G2 signatures of the
+        min-pk scheme by default; curve="bls12_381_g1" for 48-byte points); groups: the number of encodings in each
+        group.  Returns (one compressed encoding per group, flags): 0 a point, 1 the aggregate is the point at infinity
+        (its encoding; the empty group included), 2 a member did not decode (or, with check_subgroup, lies outside the
+        subgroup): the group's bytes are then meaningless."""
+        import numpy as np
+
+        sizes = [int(g) for g in groups]
+        if any(g < 0 for g in sizes):
+            raise ValueError("group sizes must not be negative")
+        offsets = np.zeros(len(sizes) + 1, dtype=np.uint64)
+        np.cumsum(sizes, out=offsets[1:])
+        eb = self.compressed_bytes(curve)
+        if len(encodings) != int(offsets[-1]) * eb:
+            raise ValueError(f"encodings must hold sum(groups) x {eb} bytes")
+        pts, fl = self.point_decompress(curve, encodings, check_subgroup=check_subgroup)
+        sums, sfl = self.point_sum(curve, pts, offsets, inf=fl)
+        return self.point_compress(curve, sums, sfl), sfl
+
+    # ---- BLS signatures (eccx_bls_*): min-pk by default, min_sig=True swaps the groups ----------------------------------
+    @staticmethod
+    def _bls_sizes(min_sig: bool):
+        """(key bytes, signature bytes)"""
+        return (96, 48) if min_sig else (48, 96)
+
+    @staticmethod
+    def _ragged(messages):
+        import numpy as np
+
+        offsets = np.zeros(len(messages) + 1, dtype=np.uint64)
+        np.cumsum([len(m) for m in messages], out=offsets[1:])
+        return b"".join(bytes(m) for m in messages), offsets
+
+    def bls_public_key(self, secrets: bytes, *, min_sig: bool = False, ct_gather: bool = False):
+        """BLS public keys of n x 32 big-endian secrets: (n compressed keys of 48 bytes, 96 with min_sig; n status bytes
+        SIGN_OK, or SIGN_NONE with zero bytes where sk = 0 or sk >= r).  The secret-scalar comb; ct_gather (min-pk only) its
+        cross-lane lookup."""
+        if len(secrets) % 32:
+            raise ValueError("secrets must be n x 32 bytes")
+        n, kb = len(secrets) // 32, self._bls_sizes(min_sig)[0]
+        out, status = ctypes.create_string_buffer(max(1, n * kb)), ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_bls_public_key(self._ctx, n, secrets, out, status,
+                                                  (BLS_MIN_SIG if min_sig else 0) | (CT_GATHER if ct_gather else 0)))
+        return out.raw[:n * kb], status.raw[:n]
+
+    def bls_sign(self, messages, secrets: bytes, dst: bytes, *, min_sig: bool = False, ct_gather: bool = False):
+        """BLS signatures sk * H(m) under the tag dst: (n compressed signatures of 96 bytes, 48 with min_sig; n status bytes).
+        No branch and no address depends on a secret; the G2 ladder spills, so this is not ecdsa_sign's promise about scratch."""
+        n = len(messages)
+        if len(secrets) != 32 * n:
+            raise ValueError("secrets must hold 32 bytes per message")
+        msgs, offsets = self._ragged(messages)
+        sb = self._bls_sizes(min_sig)[1]
+        dst = bytes(dst)
+        out, status = ctypes.create_string_buffer(max(1, n * sb)), ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_bls_sign(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, dst if dst else None, len(dst),
+                                            secrets, out, status, (BLS_MIN_SIG if min_sig else 0) | (CT_GATHER if ct_gather else 0)))
+        return out.raw[:n * sb], status.raw[:n]
+
+    def bls_verify(self, messages, sigs: bytes, pubkeys: bytes, dst: bytes, *, min_sig: bool = False) -> bytes:
+        """One SIG_* verdict per unit, MALFORMED (the signature does not decode or lies outside the subgroup) before BAD_KEY
+        (the key does not decode, lies outside the subgroup or is the identity) before the equation."""
+        n = len(messages)
+        kb, sb = self._bls_sizes(min_sig)
+        if len(sigs) != n * sb or len(pubkeys) != n * kb:
+            raise ValueError(f"sigs must be n x {sb} bytes and pubkeys n x {kb}")
+        msgs, offsets = self._ragged(messages)
+        dst = bytes(dst)
+        verdicts = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_bls_verify(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, dst if dst else None, len(dst),
+                                              sigs, pubkeys, verdicts, BLS_MIN_SIG if min_sig else 0))
+        return verdicts.raw[:n]
+
+    def bls_fast_aggregate_verify(self, messages, sigs: bytes, pubkeys: bytes, groups, dst: bytes, *, min_sig: bool = False) -> bytes:
+        """FastAggregateVerify: unit i has one message, one signature and groups[i] keys of the flat array `pubkeys`.  Every
+        key goes through KeyValidate (one bad key: SIG_BAD_KEY); the EMPTY group is SIG_BAD_KEY; a group whose keys sum to
+        the identity is not refused (with the identity signature it is SIG_VALID, as the draft has it)."""
+        import numpy as np
+
+        n = len(messages)
+        kb, sb = self._bls_sizes(min_sig)
+        key_offsets = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([int(g) for g in groups], out=key_offsets[1:])
+        keys = int(key_offsets[-1])
+        if len(groups) != n or len(sigs) != n * sb or len(pubkeys) != keys * kb:
+            raise ValueError(f"one group per message, sigs n x {sb} bytes, pubkeys sum(groups) x {kb}")
+        msgs, offsets = self._ragged(messages)
+        dst = bytes(dst)
+        verdicts = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_bls_fast_aggregate_verify(self._ctx, n, msgs if msgs else None, offsets.ctypes.data,
+                                                             dst if dst else None, len(dst), sigs, pubkeys if keys else None,
+                                                             key_offsets.ctypes.data, keys, verdicts, BLS_MIN_SIG if min_sig else 0))
+        return verdicts.raw[:n]
+
+    def bls_pop_prove(self, secrets: bytes, *, min_sig: bool = False):
+        """PopProve: each key's own bytes signed under the BLS_POP_ tag; (proofs, status)."""
+        keys, _ = self.bls_public_key(secrets, min_sig=min_sig)
+        kb = self._bls_sizes(min_sig)[0]
+        return self.bls_sign([keys[kb * i:kb * i + kb] for i in range(len(secrets) // 32)], secrets,
+                             BLS_DST_POP_PROOF_MIN_SIG if min_sig else BLS_DST_POP_PROOF, min_sig=min_sig)
+
+    def bls_pop_verify(self, pubkeys: bytes, proofs: bytes, *, min_sig: bool = False) -> bytes:
+        """PopVerify: verify of each key's own bytes under the BLS_POP_ tag."""
+        kb = self._bls_sizes(min_sig)[0]
+        return self.bls_verify([pubkeys[kb * i:kb * i + kb] for i in range(len(pubkeys) // kb)], proofs, pubkeys,
+                               BLS_DST_POP_PROOF_MIN_SIG if min_sig else BLS_DST_POP_PROOF, min_sig=min_sig)
+
+    def _bls_t(self, n, specs, stream, like):
+        import torch
+
+        self._tensors(n, *specs)
+        return torch.cuda.current_stream(like.device).cuda_stream if stream is None else stream
+
+    def _bls_msgs_t(self, msgs, offsets):
+        import torch
+
+        n = offsets.numel() - 1
+        if offsets.dtype not in (torch.int64, torch.uint64) or n < 0 or not offsets.is_contiguous() or not offsets.is_cuda:
+            raise ValueError("offsets must be a contiguous int64 CUDA tensor of n + 1 entries")
+        if not msgs.is_cuda or msgs.dtype != torch.uint8 or not msgs.is_contiguous():
+            raise ValueError("msgs must be a contiguous uint8 CUDA tensor")
+        for name, t in (("msgs", msgs), ("offsets", offsets)):
+            if t.device.index != self.device:
+                raise ValueError(f"{name}: tensor lives on cuda:{t.device.index}, this engine is bound to cuda:{self.device}")
+        if msgs.numel() == 0:  # every message empty: any valid address
+            msgs = torch.zeros((1,), dtype=torch.uint8, device=offsets.device)
+        return n, msgs
+
+    def bls_public_key_t(self, secrets, pubkeys=None, status=None, *, min_sig: bool = False, ct_gather: bool = False,
+                         stream: Optional[int] = None):
+        """Device-tensor form of bls_public_key (eccx_bls_public_key_dev); enqueued on the stream, nothing is synchronised."""
+        import torch
+
+        n, kb = self._units(secrets, 32, "secrets"), self._bls_sizes(min_sig)[0]
+        pubkeys = torch.empty((n, kb), dtype=torch.uint8, device=secrets.device) if pubkeys is None else pubkeys
+        status = torch.empty((n,), dtype=torch.uint8, device=secrets.device) if status is None else status
+        stream = self._bls_t(n, (("secrets", secrets, 32), ("pubkeys", pubkeys, kb), ("status", status, 1)), stream, secrets)
+        self._check(self._lib.eccx_bls_public_key_dev(self._ctx, n, secrets.data_ptr(), pubkeys.data_ptr(), status.data_ptr(),
+                                                      (BLS_MIN_SIG if min_sig else 0) | (CT_GATHER if ct_gather else 0), stream))
+        return pubkeys, status
+
+    def bls_sign_t(self, msgs, offsets, secrets, dst: bytes, sigs=None, status=None, *, min_sig: bool = False,
+                   ct_gather: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of bls_sign (eccx_bls_sign_dev): msgs and offsets as in hash_to_g2_t.  The offsets are not read
+        back: a lane whose offsets decrease comes back SIGN_NONE; the caller vouches that they stay inside msgs."""
+        import torch
+
+        n, msgs = self._bls_msgs_t(msgs, offsets)
+        sb = self._bls_sizes(min_sig)[1]
+        sigs = torch.empty((n, sb), dtype=torch.uint8, device=offsets.device) if sigs is None else sigs
+        status = torch.empty((n,), dtype=torch.uint8, device=offsets.device) if status is None else status
+        stream = self._bls_t(n, (("secrets", secrets, 32), ("sigs", sigs, sb), ("status", status, 1)), stream, offsets)
+        dst = bytes(dst)
+        self._check(self._lib.eccx_bls_sign_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None, len(dst),
+                                                secrets.data_ptr(), sigs.data_ptr(), status.data_ptr(),
+                                                (BLS_MIN_SIG if min_sig else 0) | (CT_GATHER if ct_gather else 0), stream))
+        return sigs, status
+
+    def bls_verify_t(self, msgs, offsets, sigs, pubkeys, dst: bytes, verdicts=None, *, min_sig: bool = False,
+                     stream: Optional[int] = None):
+        """Device-tensor form of bls_verify (eccx_bls_verify_dev); a lane whose offsets decrease is SIG_MALFORMED."""
+        import torch
+
+        n, msgs = self._bls_msgs_t(msgs, offsets)
+        kb, sb = self._bls_sizes(min_sig)
+        verdicts = torch.empty((n,), dtype=torch.uint8, device=offsets.device) if verdicts is None else verdicts
+        stream = self._bls_t(n, (("sigs", sigs, sb), ("pubkeys", pubkeys, kb), ("verdicts", verdicts, 1)), stream, offsets)
+        dst = bytes(dst)
+        self._check(self._lib.eccx_bls_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None, len(dst),
+                                                  sigs.data_ptr(), pubkeys.data_ptr(), verdicts.data_ptr(),
+                                                  BLS_MIN_SIG if min_sig else 0, stream))
+        return verdicts
+
+    def bls_fast_aggregate_verify_t(self, msgs, offsets, sigs, pubkeys, key_offsets, dst: bytes, verdicts=None, *,
+                                    min_sig: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of bls_fast_aggregate_verify: key_offsets a contiguous int64 CUDA tensor of n + 1 entries into
+        the flat array pubkeys; a key range that decreases or leaves pubkeys is SIG_MALFORMED."""
+        import torch
+
+        n, msgs = self._bls_msgs_t(msgs, offsets)
+        kb, sb = self._bls_sizes(min_sig)
+        if key_offsets.dtype not in (torch.int64, torch.uint64) or key_offsets.numel() != n + 1 or not key_offsets.is_contiguous() \
+                or not key_offsets.is_cuda or key_offsets.device.index != self.device:
+            raise ValueError("key_offsets must be a contiguous int64 CUDA tensor of n + 1 entries on this engine's GPU")
+        keys = self._units(pubkeys, kb, "pubkeys")
+        verdicts = torch.empty((n,), dtype=torch.uint8, device=offsets.device) if verdicts is None else verdicts
+        self._tensors(keys, ("pubkeys", pubkeys, kb))
+        stream = self._bls_t(n, (("sigs", sigs, sb), ("verdicts", verdicts, 1)), stream, offsets)
+        dst = bytes(dst)
+        self._check(self._lib.eccx_bls_fast_aggregate_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None,
+                                                                 len(dst), sigs.data_ptr(), pubkeys.data_ptr() if keys else None,
+                                                                 key_offsets.data_ptr(), keys, verdicts.data_ptr(),
+                                                                 BLS_MIN_SIG if min_sig else 0, stream))
+        return verdicts
 
     def msm_window_bits(self, n: int) -> int:
         """The window width msm uses for n terms (a pure function of n)."""
@@ -852,6 +1088,36 @@ class Engine:
                                     VALIDATE_POINTS if validate else 0, stream)
         self._check(rc)
         return out, flag
+
+    def point_sum_t(self, curve, points, offsets, out=None, flags=None, *, inf=None, validate: bool = False,
+                    stream: Optional[int] = None):
+        """Device-tensor form of point_sum (eccx_point_sum_dev): points and inf torch.uint8 CUDA tensors, offsets a
+        contiguous int64 CUDA tensor of n + 1 entries, relative to offsets[0].  Enqueued on `stream` (default: torch's
+        current stream), nothing is synchronised and the offsets are not read back: a group whose range decreases or ends
+        beyond the records of `points` comes back FLAG_REJECTED, having read nothing.  Returns (out n x 2FB, flags n)."""
+        import torch
+
+        cid = curve_id(curve)
+        pb = 2 * field_bytes(cid)
+        n = offsets.numel() - 1
+        if offsets.dtype not in (torch.int64, torch.uint64) or n < 0 or not offsets.is_contiguous() or not offsets.is_cuda:
+            raise ValueError("offsets must be a contiguous int64 CUDA tensor of n + 1 entries")
+        if offsets.device.index != self.device:
+            raise ValueError(f"offsets: tensor lives on cuda:{offsets.device.index}, this engine is bound to cuda:{self.device}")
+        members = self._units(points, pb, "points")
+        self._tensors(members, ("points", points, pb), ("inf", inf, 1))
+        if out is None:
+            out = torch.empty((n, pb), dtype=torch.uint8, device=offsets.device)
+        if flags is None:
+            flags = torch.empty((n,), dtype=torch.uint8, device=offsets.device)
+        self._tensors(n, ("out", out, pb), ("flags", flags, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(offsets.device).cuda_stream
+        rc = self._lib.eccx_point_sum_dev(self._ctx, cid, n, offsets.data_ptr(), members, points.data_ptr() if members else None,
+                                          inf.data_ptr() if (inf is not None and members) else None, out.data_ptr(),
+                                          flags.data_ptr(), VALIDATE_POINTS if validate else 0, stream)
+        self._check(rc)
+        return out, flags
 
     def double_scalarmul_t(self, curve, u1, u2, q, out=None, flags=None, *, subtract: bool = False,
                            validate: bool = False, x_only: bool = False, stream: Optional[int] = None):

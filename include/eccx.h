@@ -234,6 +234,9 @@ enum {
   ECCX_H2C_NU = 1u << 13,          /* eccx_hash_to_g1, eccx_hash_to_g2: the nonuniform suite BLS12381G1_XMD:SHA-256_SSWU_NU_
                                       (BLS12381G2_...; encode_to_curve: one field element, one map) instead of ..._RO_
                                       (hash_to_curve) */
+  ECCX_BLS_MIN_SIG = 1u << 14,     /* eccx_bls_*: the minimal-signature-size variant -- 96-byte keys in G2, 48-byte signatures in G1,
+                                      H(m) = hash_to_g1 -- instead of the default min-pk (Ethereum's: 48-byte keys in G1,
+                                      96-byte signatures in G2, H(m) = hash_to_g2) */
   ECCX_ASSUME_SUBGROUP = 1u << 9   /* eccx_scalarmul_var, bls12_381_g1: the caller guarantees every base point
                                       is in the prime-order subgroup G1 (e.g. it was decoded under
                                       ECCX_CHECK_SUBGROUP, or is a multiple of the generator).  The
@@ -275,6 +278,9 @@ enum {
   ECCX_PREP_MSM = 1u << 14,     /* eccx_reserve (bls12_381_g1): the workspace of eccx_msm for every n <= max_n (at 2^20 terms
                                    about 0.65 GB: the converted terms, the grouped list, the partial sums and the bucket
                                    rows); with ECCX_PREP_HOST the copies of the host form's scalars, points and flags */
+  ECCX_PREP_BLS = 1u << 15,     /* eccx_reserve (bls12_381_g2): the working slab of the eccx_bls_* entry points for max(n, keys) <=
+                                   max_n, and with it what the hash, the pairing (pairs = 2), the decoders, the group sum and the
+                                   secret-scalar ladders need on both curves (the comb tables are eccx_prepare's) */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -609,6 +615,90 @@ int eccx_msm_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, cons
                  void* d_flag, uint32_t opts, void* stream);
 /* The window width c (bits) eccx_msm uses for n terms: ceil(257 / c) windows of 2^(c-1) buckets.  Non-decreasing in n. */
 int eccx_msm_window_bits(size_t n);
+
+/* Sums of ragged groups of points: ONE result per GROUP, out[g] = the sum of the group's members -- what aggregating the
+ * public keys of a committee (BLS FastAggregateVerify) or a set of signatures takes.  eccx_point_add makes one result
+ * per pair and eccx_msm one per call; here each group is summed by one wavefront, or by one lane where it has at most 7
+ * members (two kernels per call; each group is taken by exactly one of them, by its own length, on the device).
+ *   curve   : ECCX_BLS12_381_G1 or ECCX_BLS12_381_G2; any other valid id is ECCX_ERR_ARG, an invalid one ECCX_ERR_CURVE
+ *   offsets : n + 1 values, relative to offsets[0] as the message offsets of eccx_hash_to_g2 are: group g is the members
+ *             offsets[g] - offsets[0] .. offsets[g + 1] - offsets[0]
+ *   points  : `members` affine x || y records of 96 (G1) or 192 (G2) bytes, as every entry point of the curve writes them.
+ *             Any point of the curve is legal, in the prime-order subgroup or not.
+ *   inf     : NULL or `members` flag bytes as the other entry points write them: 1 -- the member contributes nothing,
+ *             whatever its coordinate bytes are; 2 -- a rejected operand, which rejects its group (eccx_point_add's rule)
+ *   out     : n records; flags: n bytes -- 0 a point, ECCX_FLAG_INFINITY the sum is the point at infinity (zero bytes;
+ *             the empty group included), ECCX_FLAG_REJECTED (zero bytes)
+ *   opts    : 0 or ECCX_VALIDATE_POINTS (a member not flagged 1 with a coordinate >= p or off the curve rejects its group).
+ *             Every other bit is ECCX_ERR_ARG, returned before anything is launched or written.  Without
+ *             ECCX_VALIDATE_POINTS garbage input gives an unspecified result, never an out-of-bounds access.
+ * n == 0 returns ECCX_OK whatever the pointers are.  The host form checks that the offsets never decrease and that the
+ * last one stays within `members` before it touches the device (ECCX_ERR_ARG).  The _dev form cannot read them: a group
+ * whose range decreases or ends beyond `members` gets ECCX_FLAG_REJECTED and reads nothing, and the other groups stand.
+ * Equal members, opposite members and partial sums at infinity are no special cases (the addition is complete), and no
+ * lane's chain of additions exceeds ceil(len / 64) + 6 whatever the group.  The _dev form enqueues on `stream` and
+ * returns; it works in the context's row buffer, so after eccx_reserve(ctx, curve, max_n, 0) a call with n <= max_n
+ * neither allocates, frees nor synchronises.  Nothing is read back and the result does not depend on timing: the same
+ * input gives the same bytes. */
+int eccx_point_sum(eccx_ctx* ctx, int curve, size_t n, const uint64_t* offsets, size_t members, const uint8_t* points,
+                   const uint8_t* inf, uint8_t* out, uint8_t* flags, uint32_t opts);
+int eccx_point_sum_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_offsets, size_t members, const void* d_points,
+                       const void* d_inf, void* d_out, void* d_flags, uint32_t opts, void* stream);
+
+/* BLS signatures on BLS12-381 (draft-irtf-cfrg-bls-signature): keys, signatures, verification and FastAggregateVerify, wire
+ * bytes in, status or verdict bytes out, every step on the device on one stream.
+ * Variant: min-pk by default (Ethereum's): public keys 48-byte zcash-compressed G1, signatures 96-byte compressed G2, H(m) =
+ * hash_to_g2.  ECCX_BLS_MIN_SIG swaps the groups: keys 96 bytes, signatures 48 bytes, H(m) = hash_to_g1.
+ * Messages are ragged by n + 1 offsets and the domain separation tag is a host-side argument, exactly as in
+ * eccx_hash_to_g2.  The basic, message-augmentation and proof-of-possession schemes differ only in the tag and in what the
+ * caller puts into the message; PopProve / PopVerify are sign / verify of the key's own bytes under the BLS_POP_... tag.
+ *   eccx_bls_public_key  secrets n x 32 big-endian -> pubkeys n x 48 (96); status n: ECCX_SIGN_OK, or ECCX_SIGN_NONE with zero
+ *                        bytes where sk = 0 or sk >= r.  The secret-scalar fixed-base comb (ECCX_CT_SCAN implied), the
+ *                        normalisation, the compressor, and a range test done with masks only.
+ *   eccx_bls_sign        sigs n x 96 (48) = sk * H(m): the hash, the secret-scalar ladder (min-sig: G1 with ECCX_CT_SCAN |
+ *                        ECCX_ASSUME_SUBGROUP; min-pk: G2 with ECCX_CT_SCAN), the compressor.  status as for keys; a lane whose
+ *                        offsets decrease is ECCX_SIGN_NONE too.  An out-of-range secret is replaced by 1 through a mask before
+ *                        the ladder and its output zeroed afterwards, so it steers neither a branch nor an address.
+ *                        SIDE CHANNELS: the promise is exactly that of the entry points underneath -- no branch and no address
+ *                        depends on sk.  It is NOT the stronger promise eccx_ecdsa_sign makes about scratch memory: the G2
+ *                        ladder spills.  The slab's copy of the secrets is wiped by the call, on its error paths too; the host forms wipe their
+ *                        device copies as well.
+ *   eccx_bls_verify      verdicts n x ECCX_SIG_*, MALFORMED before BAD_KEY before the equation.  ECCX_SIG_MALFORMED: the
+ *                        signature's bytes do not decode, the point is outside the subgroup, or the message's offsets
+ *                        decrease.  ECCX_SIG_BAD_KEY: the key does not decode, is outside the subgroup, or is the identity
+ *                        (KeyValidate).  Otherwise ECCX_SIG_VALID iff e(pk, H(m)) e(-G1, sig) = 1 (min-sig: e(sig, -G2)
+ *                        e(H(m), pk) = 1).  A signature that is the identity is a legal point: the equation decides.
+ *   eccx_bls_fast_aggregate_verify   unit i has one message, one signature and the keys key_offsets[i] .. key_offsets[i + 1]
+ *                        (relative to key_offsets[0]) of a flat array of `keys` encodings.  Every key goes through
+ *                        KeyValidate: one bad key makes the unit ECCX_SIG_BAD_KEY.  The EMPTY group is ECCX_SIG_BAD_KEY (the
+ *                        draft makes n >= 1 a precondition; the equation would accept the identity signature for it).  The
+ *                        keys are summed by eccx_point_sum's kernels and the unit verified as above.  A group whose keys SUM to
+ *                        the identity is NOT refused: the draft checks each key, not the aggregate, so with the identity
+ *                        signature such a unit is ECCX_SIG_VALID.  A key range that decreases or leaves `keys` is
+ *                        ECCX_SIG_MALFORMED.
+ * opts other than 0 or ECCX_BLS_MIN_SIG is ECCX_ERR_ARG.  Signing and key derivation also take ECCX_CT_GATHER for min-pk: it
+ * selects the lane-gather lookup of the G1 comb in key derivation; signing accepts it and it changes nothing there (the
+ * ladders have no gather form).
+ * n == 0 returns ECCX_OK; null buffers and decreasing message offsets in the host forms are ECCX_ERR_ARG, as in
+ * eccx_hash_to_g2.  After eccx_prepare (ECCX_PREP_CT on the keys' curve, for key derivation) and eccx_reserve(ctx,
+ * ECCX_BLS12_381_G2, max_n, ECCX_PREP_BLS) a _dev call with max(n, keys) <= max_n neither allocates, frees nor synchronises. */
+int eccx_bls_public_key(eccx_ctx* ctx, size_t n, const uint8_t* secrets, uint8_t* pubkeys, uint8_t* status, uint32_t opts);
+int eccx_bls_public_key_dev(eccx_ctx* ctx, size_t n, const void* d_secrets, void* d_pubkeys, void* d_status, uint32_t opts,
+                            void* stream);
+int eccx_bls_sign(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                  const uint8_t* secrets, uint8_t* sigs, uint8_t* status, uint32_t opts);
+int eccx_bls_sign_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                      const void* d_secrets, void* d_sigs, void* d_status, uint32_t opts, void* stream);
+int eccx_bls_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                    const uint8_t* sigs, const uint8_t* pubkeys, uint8_t* verdicts, uint32_t opts);
+int eccx_bls_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                        const void* d_sigs, const void* d_pubkeys, void* d_verdicts, uint32_t opts, void* stream);
+int eccx_bls_fast_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                                   size_t dst_len, const uint8_t* sigs, const uint8_t* pubkeys, const uint64_t* key_offsets,
+                                   size_t keys, uint8_t* verdicts, uint32_t opts);
+int eccx_bls_fast_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
+                                       size_t dst_len, const void* d_sigs, const void* d_pubkeys, const void* d_key_offsets,
+                                       size_t keys, void* d_verdicts, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

@@ -41,6 +41,7 @@ pub const ECCX_SUBTRACT: u32 = 1 << 5;
 pub const ECCX_CHECK_SUBGROUP: u32 = 1 << 6;
 pub const ECCX_UNCOMPRESSED: u32 = 1 << 7;
 pub const ECCX_CT_SCAN: u32 = 1 << 8;
+pub const ECCX_BLS_MIN_SIG: u32 = 1 << 14; // eccx_bls_*: keys in G2, signatures in G1
 pub const ECCX_ASSUME_SUBGROUP: u32 = 1 << 9;
 pub const ECCX_CT_GATHER: u32 = 1 << 10;
 pub const ECCX_OUT_X_ONLY: u32 = 1 << 11;
@@ -64,6 +65,7 @@ pub const ECCX_PREP_ECDSA_SIGN: u32 = 1 << 10; // eccx_ecdsa_sign's / eccx_ecdsa
 pub const ECCX_PREP_H2C: u32 = 1 << 11; // eccx_hash_to_g1's / eccx_hash_to_g2's result rows
 pub const ECCX_PREP_PAIRING: u32 = 1 << 12; // eccx_pairing's / eccx_pairing_check's slab and rows
 pub const ECCX_PREP_X448: u32 = 1 << 13; // eccx_x448's result rows (any curve id) and, with ECCX_PREP_HOST, its copies
+pub const ECCX_PREP_BLS: u32 = 1 << 15; // the working slab of the eccx_bls_* entry points (bls12_381_g2)
 pub const ECCX_PREP_MSM: u32 = 1 << 14; // eccx_msm's workspace for every n <= max_n (bls12_381_g1)
 
 // per-unit flags
@@ -190,6 +192,34 @@ extern "C" {
     pub fn eccx_msm_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_scalars: *const c_void, d_points: *const c_void,
                         d_inf: *const c_void, d_out: *mut c_void, d_flag: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
     pub fn eccx_msm_window_bits(n: usize) -> c_int;
+
+    // ONE sum per ragged group of points on BLS12-381 G1 or G2: aggregating public keys or signatures
+    pub fn eccx_point_sum(ctx: *mut eccx_ctx, curve: c_int, n: usize, offsets: *const u64, members: usize, points: *const u8,
+                          inf: *const u8, out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_point_sum_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_offsets: *const c_void, members: usize,
+                              d_points: *const c_void, d_inf: *const c_void, d_out: *mut c_void, d_flags: *mut c_void, opts: u32,
+                              stream: *mut c_void) -> c_int;
+
+    // BLS signatures: keys, signatures, verification, FastAggregateVerify (min-pk; ECCX_BLS_MIN_SIG swaps the groups)
+    pub fn eccx_bls_public_key(ctx: *mut eccx_ctx, n: usize, secrets: *const u8, pubkeys: *mut u8, status: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_bls_public_key_dev(ctx: *mut eccx_ctx, n: usize, d_secrets: *const c_void, d_pubkeys: *mut c_void, d_status: *mut c_void,
+                                   opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_bls_sign(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8, dst_len: usize,
+                         secrets: *const u8, sigs: *mut u8, status: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_bls_sign_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8, dst_len: usize,
+                             d_secrets: *const c_void, d_sigs: *mut c_void, d_status: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_bls_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8, dst_len: usize,
+                           sigs: *const u8, pubkeys: *const u8, verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_bls_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8,
+                               dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
+                               stream: *mut c_void) -> c_int;
+    pub fn eccx_bls_fast_aggregate_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8,
+                                          dst_len: usize, sigs: *const u8, pubkeys: *const u8, key_offsets: *const u64, keys: usize,
+                                          verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_bls_fast_aggregate_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void,
+                                              dst: *const u8, dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void,
+                                              d_key_offsets: *const c_void, keys: usize, d_verdicts: *mut c_void, opts: u32,
+                                              stream: *mut c_void) -> c_int;
 
     // X25519 over a batch                                    protocol::x25519::x25519
     pub fn eccx_x25519(ctx: *mut eccx_ctx, n: usize, scalars: *const u8, u: *const u8, out: *mut u8, flags: *mut u8,
