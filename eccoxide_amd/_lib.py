@@ -63,6 +63,14 @@ SYMBOLS = {
     "eccx_pairing_check": (c_int, [c_void_p, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_pairing_check_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_pairing_lanes": (c_size_t, [c_void_p]),
+    "eccx_pairing_groups": (c_int, [c_void_p, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_pairing_groups_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_uint32, c_void_p]),
+    "eccx_pairing_check_groups": (c_int, [c_void_p, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_pairing_check_groups_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_uint32, c_void_p]),
+    "eccx_pairing_group_chunk": (c_int, []),
+    "eccx_pairing_group_fanin": (c_int, []),
     "eccx_msm": (c_int, [c_void_p, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_msm_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_msm_window_bits": (c_int, [c_size_t]),
@@ -77,6 +85,9 @@ SYMBOLS = {
     "eccx_bls_fast_aggregate_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, c_uint32]),
     "eccx_bls_fast_aggregate_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p,
                                                    c_size_t, c_void_p, c_uint32, c_void_p]),
+    "eccx_bls_aggregate_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, c_uint32]),
+    "eccx_bls_aggregate_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                              c_size_t, c_void_p, c_uint32, c_void_p]),
     "eccx_comb_table": (c_int, [c_void_p, c_int, _u8p]),
     "eccx_scalarmul_var_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_scalarmul_base_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, c_uint32]),

@@ -56,8 +56,9 @@ const CurveOps* ops_of(int curve) {
 //              host-buffer forms fill with their copies
 //   B_MSM      the workspace of eccx_msm_dev (kernels_msm.hpp lays it out)
 //   B_BLS      the working slab of the eccx_bls_* entry points (BlsSlab below)
+//   B_BLSAGG   the working slab of eccx_bls_aggregate_verify (BlsAggSlab below)
 enum { IO_K = 0, IO_P = 1, IO_O = 2, IO_F = 3, IO_J = 4, IO_A = 5, IO_B = 6, NIO = 7 };
-enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, NBUF };
+enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, NBUF };
 struct DevBuf {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -208,6 +209,34 @@ int ensure_pairing(eccx_ctx* ctx, const PairingNeed& nd) {
   return rc ? rc : grow(ctx, B_ROWS, nd.f_bytes + nd.term_bytes);
 }
 
+// What the ragged pairing product needs for n groups over `terms` terms: the chunk slots, the slab of its persistent
+// kernels and of the final exponentiation, and in the row buffer the groups' Miller values, the terms, the chunk values
+// (all [block][word][lane] rows), the n + 1 chunk starts and a byte per term.  Every piece grows with n and with terms, so
+// what (max_n, max_n) needs holds every shape with n + terms <= max_n.
+struct PairingGroupsNeed {
+  int finalexp_grid;
+  size_t slots, slab_bytes, f_bytes, t_bytes, c_bytes, cstart_bytes, tflag_bytes;
+  size_t rows_bytes() const { return f_bytes + t_bytes + c_bytes + cstart_bytes + tflag_bytes; }
+};
+PairingGroupsNeed need_pairing_groups(const eccx_ctx* ctx, const CurveOps* ops, size_t n, size_t terms) {
+  const size_t wg = eccx::LAUNCH_WG, row = (size_t)ops->pairing_row_words * wg * sizeof(uint32_t);
+  PairingGroupsNeed nd;
+  nd.slots = n + terms / (size_t)ops->pairing_group_chunk;
+  nd.finalexp_grid = ops->pairing_finalexp_grid(ctx->cus, n);
+  nd.slab_bytes = (size_t)std::max(ops->pairing_groups_grid(ctx->cus, nd.slots), nd.finalexp_grid) * (size_t)ops->pairing_slab_words * wg *
+                  sizeof(uint32_t);
+  nd.f_bytes = (n + wg - 1) / wg * row;
+  nd.t_bytes = (terms + wg - 1) / wg * row;
+  nd.c_bytes = (nd.slots + wg - 1) / wg * row;
+  nd.cstart_bytes = (n + 1 + 3) / 4 * 4 * sizeof(uint32_t);
+  nd.tflag_bytes = terms;
+  return nd;
+}
+int ensure_pairing_groups(eccx_ctx* ctx, const PairingGroupsNeed& nd) {
+  const int rc = grow(ctx, B_SCRATCH, nd.slab_bytes);
+  return rc ? rc : grow(ctx, B_ROWS, nd.rows_bytes());
+}
+
 // result rows for n units
 int ensure_rows(eccx_ctx* ctx, const CurveOps* ops, size_t n) {
   return grow(ctx, B_ROWS, n * (size_t)ops->info.jac_words * sizeof(uint32_t));
@@ -275,6 +304,29 @@ struct BlsSlab {
             c.take(n * 192), c.take(n), c.take(n * 192), c.take(n * 384), c.take(2 * n), c.take(2 * n), c.take(n)};
   }
 };
+// AggregateVerify, n units over `terms` (key, message) pairs, records at the wider group's size as above: the decoded keys
+// and H(m) of the pairs (terms x 192 each) and the decoded signatures (n x 192) with their flags; the flat terms of the
+// ragged pairing product (terms + n: g1 x 96, g2 x 192, a flag byte each per side) with their n + 1 offsets; what the
+// pairs' flags decide per unit (n words); the pairing's verdicts (n).  Every piece grows with n and with terms.
+struct BlsAggSlab {
+  uint8_t *key, *key_fl, *sig, *sig_fl, *h, *h_fl, *g1, *g2, *g1_inf, *g2_inf, *toff, *pre, *pv;
+  static BlsAggSlab lay(Carve& c, size_t n, size_t terms) {
+    const size_t flat = terms + n;
+    return {c.take(terms * 192), c.take(terms), c.take(n * 192), c.take(n), c.take(terms * 192), c.take(terms), c.take(flat * 96),
+            c.take(flat * 192), c.take(flat), c.take(flat), c.take((n + 1) * sizeof(uint64_t)), c.take(n * sizeof(uint32_t)), c.take(n)};
+  }
+};
+// out == nullptr: only size the slab (eccx_reserve)
+int ensure_bls_agg_slab(eccx_ctx* ctx, size_t n, size_t terms, BlsAggSlab* out) {
+  Carve size{nullptr};
+  BlsAggSlab::lay(size, n, terms);
+  uint8_t* base = nullptr;
+  const int rc = grow(ctx, B_BLSAGG, size.end, &base);
+  if (rc || !out) return rc;
+  Carve c{base};
+  *out = BlsAggSlab::lay(c, n, terms);
+  return ECCX_OK;
+}
 // out == nullptr: only size the slab (eccx_reserve)
 template <class Slab>
 int ensure_slab(eccx_ctx* ctx, int which, const CurveOps* ops, size_t n, Slab* out) {
@@ -959,6 +1011,18 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     if (!rc) rc = ensure_work(ctx, g1, max_n, {need_var_ct(ctx, g1, max_n, false), need_var_ct(ctx, g1, max_n, true), need_var_fixup(ctx, g1, max_n)});
     if (!rc) rc = ensure_pairing(ctx, need_pairing(ctx, g2, max_n, 2));
   }
+  // eccx_pairing_groups / eccx_pairing_check_groups: every shape with n + terms <= max_n
+  if (!rc && (what & ECCX_PREP_PAIRING_GROUPS) && ops->pairing_groups)
+    rc = ensure_pairing_groups(ctx, need_pairing_groups(ctx, ops, max_n, max_n));
+  // eccx_bls_aggregate_verify, n + terms <= max_n: its slab, the hash's rows on either curve (two per message on G2) and the
+  // ragged product over terms + n flat terms
+  if (!rc && (what & ECCX_PREP_BLS_AGGREGATE)) {
+    rc = ensure_bls_agg_slab(ctx, max_n, max_n, nullptr);
+    const CurveOps *g1 = ops_of(ECCX_BLS12_381_G1), *g2 = ops_of(ECCX_BLS12_381_G2);
+    if (!rc) rc = ensure_rows(ctx, g2, 2 * max_n);
+    if (!rc) rc = ensure_rows(ctx, g1, max_n);
+    if (!rc) rc = ensure_pairing_groups(ctx, need_pairing_groups(ctx, g2, max_n, max_n));
+  }
   // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
   // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
   return rc;
@@ -1603,6 +1667,104 @@ int eccx_pairing_check(eccx_ctx* ctx, size_t n, size_t pairs, const uint8_t* g1,
   return pairing_host(ctx, n, pairs, g1, g1_inf, g2, g2_inf, nullptr, false, verdicts, opts);
 }
 
+namespace {
+// eccx_pairing_groups and eccx_pairing_check_groups are one body, as eccx_pairing and eccx_pairing_check are
+constexpr size_t PAIRING_GROUPS_MAX = (size_t)1 << 31;  // n + terms: the chunk starts are 32-bit
+const char* const PAIRING_GROUPS_RANGE_MSG = "eccx_pairing_groups: n + terms above 2^31";
+int pairing_groups_dev(eccx_ctx* ctx, size_t n, size_t terms, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                       const void* d_g2_inf, const void* d_offsets, void* d_out, bool want_value, void* d_status, uint32_t opts,
+                       void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS) return arg_err(ctx, PAIRING_OPTS_MSG);
+  if (n == 0) return ECCX_OK;
+  if (n > PAIRING_GROUPS_MAX || terms > PAIRING_GROUPS_MAX - n) return arg_err(ctx, PAIRING_GROUPS_RANGE_MSG);
+  if (int rc = begin_batch(ctx, d_offsets && d_status && (d_out || !want_value) && (terms == 0 || (d_g1 && d_g2)))) return rc;
+  const CurveOps* ops = ops_of(ECCX_BLS12_381_G2);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const PairingGroupsNeed nd = need_pairing_groups(ctx, ops, n, terms);
+  if (int rc = ensure_pairing_groups(ctx, nd)) return rc;
+  uint8_t* rows = ctx->buf[B_ROWS].p;
+  uint32_t* fbuf = reinterpret_cast<uint32_t*>(rows);
+  uint32_t* tbuf = reinterpret_cast<uint32_t*>(rows + nd.f_bytes);
+  uint32_t* cbuf = reinterpret_cast<uint32_t*>(rows + nd.f_bytes + nd.t_bytes);
+  uint32_t* cstart = reinterpret_cast<uint32_t*>(rows + nd.f_bytes + nd.t_bytes + nd.c_bytes);
+  uint8_t* tflag = rows + nd.f_bytes + nd.t_bytes + nd.c_bytes + nd.cstart_bytes;
+  uint8_t* status = static_cast<uint8_t*>(d_status);
+  HIP_TRY(ctx, ops->pairing_groups(s, ctx->cus, n, terms, static_cast<const uint64_t*>(d_offsets), static_cast<const uint8_t*>(d_g1),
+                                   static_cast<const uint8_t*>(d_g1_inf), static_cast<const uint8_t*>(d_g2),
+                                   static_cast<const uint8_t*>(d_g2_inf), tbuf, cbuf, fbuf, cstart, tflag, status, ctx->scratch(),
+                                   kopts_of(opts)));
+  HIP_TRY(ctx, ops->pairing_finalexp(nd.finalexp_grid, s, n, fbuf, want_value ? static_cast<uint8_t*>(d_out) : nullptr, status,
+                                     ctx->scratch()));
+  return ECCX_OK;
+}
+int pairing_groups_host(eccx_ctx* ctx, size_t n, size_t terms, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                        const uint8_t* g2_inf, const uint64_t* offsets, uint8_t* out, bool want_value, uint8_t* status, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS) return arg_err(ctx, PAIRING_OPTS_MSG);
+  if (n == 0) return ECCX_OK;
+  if (n > PAIRING_GROUPS_MAX || terms > PAIRING_GROUPS_MAX - n) return arg_err(ctx, PAIRING_GROUPS_RANGE_MSG);
+  if (!offsets || !status || (want_value && !out) || (terms && (!g1 || !g2))) return arg_err(ctx, "null buffer");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return arg_err(ctx, "eccx_pairing_groups: the offsets decrease");
+  if (offsets[n] - offsets[0] > terms) return arg_err(ctx, "eccx_pairing_groups: the last offset lies beyond the terms");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // n + 1 offsets and `terms` records and flags in, n values or verdicts out, through the I/O slots of the other host forms
+  uint8_t *d_off = nullptr, *d_1 = nullptr, *d_2 = nullptr, *d_i1 = nullptr, *d_i2 = nullptr, *d_o = nullptr, *d_f = nullptr;
+  int rc = grow(ctx, B_IO + IO_J, (n + 1) * sizeof(uint64_t), &d_off);
+  if (!rc) rc = grow(ctx, B_IO + IO_F, n, &d_f);
+  if (!rc && want_value) rc = grow(ctx, B_IO + IO_O, n * 576, &d_o);
+  if (!rc && terms) rc = grow(ctx, B_IO + IO_K, terms * 96, &d_1);
+  if (!rc && terms) rc = grow(ctx, B_IO + IO_P, terms * 192, &d_2);
+  if (!rc && terms && g1_inf) rc = grow(ctx, B_IO + IO_A, terms, &d_i1);
+  if (!rc && terms && g2_inf) rc = grow(ctx, B_IO + IO_B, terms, &d_i2);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  HIP_TRY(ctx, settled(hipMemcpyAsync(d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s)));
+  if (terms) {
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_1, g1, terms * 96, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_2, g2, terms * 192, hipMemcpyHostToDevice, s)));
+    if (g1_inf) HIP_TRY(ctx, settled(hipMemcpyAsync(d_i1, g1_inf, terms, hipMemcpyHostToDevice, s)));
+    if (g2_inf) HIP_TRY(ctx, settled(hipMemcpyAsync(d_i2, g2_inf, terms, hipMemcpyHostToDevice, s)));
+  }
+  rc = pairing_groups_dev(ctx, n, terms, d_1, d_i1, d_2, d_i2, d_off, d_o, want_value, d_f, opts, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  if (want_value) HIP_TRY(ctx, settled(hipMemcpyAsync(out, d_o, n * 576, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, settled(hipMemcpyAsync(status, d_f, n, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
+}
+}  // namespace
+
+int eccx_pairing_groups_dev(eccx_ctx* ctx, size_t n, size_t terms, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                            const void* d_g2_inf, const void* d_term_offsets, void* d_out, void* d_flags, uint32_t opts,
+                            void* stream) {
+  return pairing_groups_dev(ctx, n, terms, d_g1, d_g1_inf, d_g2, d_g2_inf, d_term_offsets, d_out, true, d_flags, opts, stream);
+}
+int eccx_pairing_groups(eccx_ctx* ctx, size_t n, size_t terms, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                        const uint8_t* g2_inf, const uint64_t* term_offsets, uint8_t* out, uint8_t* flags, uint32_t opts) {
+  return pairing_groups_host(ctx, n, terms, g1, g1_inf, g2, g2_inf, term_offsets, out, true, flags, opts);
+}
+int eccx_pairing_check_groups_dev(eccx_ctx* ctx, size_t n, size_t terms, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                                  const void* d_g2_inf, const void* d_term_offsets, void* d_verdicts, uint32_t opts,
+                                  void* stream) {
+  return pairing_groups_dev(ctx, n, terms, d_g1, d_g1_inf, d_g2, d_g2_inf, d_term_offsets, nullptr, false, d_verdicts, opts, stream);
+}
+int eccx_pairing_check_groups(eccx_ctx* ctx, size_t n, size_t terms, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                              const uint8_t* g2_inf, const uint64_t* term_offsets, uint8_t* verdicts, uint32_t opts) {
+  return pairing_groups_host(ctx, n, terms, g1, g1_inf, g2, g2_inf, term_offsets, nullptr, false, verdicts, opts);
+}
+int eccx_pairing_group_chunk(void) { return ops_of(ECCX_BLS12_381_G2)->pairing_group_chunk; }
+int eccx_pairing_group_fanin(void) { return ops_of(ECCX_BLS12_381_G2)->pairing_group_fanin; }
+
 int eccx_msm_window_bits(size_t n) { return msm_window_bits(n); }
 
 int eccx_msm_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, const void* d_points, const void* d_inf, void* d_out,
@@ -1850,6 +2012,44 @@ int bls_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_of
   return ECCX_OK;
 }
 
+// eccx_bls_aggregate_verify_dev: the decoders, the hash, the ragged assembly, the ragged product, the fold, on one stream
+const char* const BLS_AGG_OPTS = "eccx_bls_aggregate_verify: opts must be 0 or ECCX_BLS_MIN_SIG";
+int bls_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                             const void* d_sigs, const void* d_pubkeys, const void* d_group_offsets, size_t terms, void* d_verdicts,
+                             uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_AGG_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (n > PAIRING_GROUPS_MAX / 2 || terms > PAIRING_GROUPS_MAX / 2 - n) return arg_err(ctx, "eccx_bls_aggregate_verify: n + terms above 2^30");
+  if (int rc = begin_batch(ctx, d_sigs && d_group_offsets && d_verdicts && (dst || dst_len == 0) &&
+                                    (terms == 0 || (d_msgs && d_offsets && d_pubkeys))))
+    return rc;
+  const BlsWhat& w = *bls_what(opts);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BlsAggSlab b;
+  if (int rc = ensure_bls_agg_slab(ctx, n, terms, &b)) return rc;
+  uint8_t* verdicts = static_cast<uint8_t*>(d_verdicts);
+  const uint64_t* go = static_cast<const uint64_t*>(d_group_offsets);
+  uint32_t* pre = reinterpret_cast<uint32_t*>(b.pre);
+  HIP_TRY(ctx, hipMemsetAsync(pre, 0, n * sizeof(uint32_t), s));
+  if (terms) {
+    // every key through the decoder, its subgroup test and KeyValidate (the identity is no key); every message through the hash
+    if (int rc = eccx_point_decompress_dev(ctx, w.key_curve, terms, d_pubkeys, b.key, b.key_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+    HIP_TRY(ctx, eccx::launch_bls_key_flags(s, terms, b.key_fl));
+  }
+  if (int rc = eccx_point_decompress_dev(ctx, w.sig_curve, n, d_sigs, b.sig, b.sig_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+  if (terms) {
+    // the hash's output lands in the slab before the pairing reuses the rows it worked in (one stream: ordered)
+    if (int rc = hash_to_curve_dev(ctx, *w.h2c, terms, d_msgs, d_offsets, dst, dst_len, b.h, b.h_fl, 0, s)) return rc;
+    HIP_TRY(ctx, eccx::launch_bls_group_flags(s, n, terms, go, b.key_fl, b.h_fl, pre));
+  }
+  HIP_TRY(ctx, eccx::launch_bls_assemble_groups(s, n, terms, w.min_sig, b.key, b.key_fl, b.sig, b.sig_fl, b.h, b.h_fl, go, pre, b.g1,
+                                                b.g1_inf, b.g2, b.g2_inf, reinterpret_cast<uint64_t*>(b.toff), verdicts));
+  if (int rc = pairing_groups_dev(ctx, n, terms + n, b.g1, b.g1_inf, b.g2, b.g2_inf, b.toff, nullptr, false, b.pv, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_bls_fold(s, n, b.pv, verdicts));
+  return ECCX_OK;
+}
+
 // the host forms: messages as eccx_hash_to_g2 takes them, one chunk (the kernels dwarf the copies)
 int bls_msgs_host(eccx_ctx* ctx, size_t n, EdMsgs& m, const uint8_t* dst, size_t dst_len, bool others_ok, const char* decrease) {
   if (!m.offsets || !others_ok || (!dst && dst_len != 0)) return arg_err(ctx, "null buffer");
@@ -1948,6 +2148,62 @@ int eccx_bls_fast_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs,
         return bls_verify_dev(ctx, cnt, m.dev_msgs(lo), m.dev_offsets(lo), dst, dst_len, d[0], d_keys, true, d_ko, keys, d[1], opts, ctx->stream);
       },
       [&](size_t lo, size_t cnt, hipStream_t st) { return m.copy_in(lo, cnt, st); });
+}
+
+int eccx_bls_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
+                                  size_t dst_len, const void* d_sigs, const void* d_pubkeys, const void* d_group_offsets,
+                                  size_t terms, void* d_verdicts, uint32_t opts, void* stream) {
+  return bls_aggregate_verify_dev(ctx, n, d_msgs, d_offsets, dst, dst_len, d_sigs, d_pubkeys, d_group_offsets, terms, d_verdicts, opts,
+                                  stream);
+}
+int eccx_bls_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                              size_t dst_len, const uint8_t* sigs, const uint8_t* pubkeys, const uint64_t* group_offsets,
+                              size_t terms, uint8_t* verdicts, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_AGG_OPTS)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (n > PAIRING_GROUPS_MAX / 2 || terms > PAIRING_GROUPS_MAX / 2 - n) return arg_err(ctx, "eccx_bls_aggregate_verify: n + terms above 2^30");
+  if (!sigs || !group_offsets || !verdicts || (!dst && dst_len != 0) || (terms && (!offsets || !pubkeys))) return arg_err(ctx, "null buffer");
+  for (size_t i = 0; i < n; ++i)
+    if (group_offsets[i + 1] < group_offsets[i]) return arg_err(ctx, "eccx_bls_aggregate_verify: the group offsets decrease");
+  if (group_offsets[n] - group_offsets[0] > terms) return arg_err(ctx, "eccx_bls_aggregate_verify: the last group offset lies beyond the terms");
+  // the messages are per PAIR: `terms` of them, copied whole with the keys and the group offsets ahead of the one chunk
+  EdMsgs m{msgs, offsets};
+  if (terms) {
+    if (int rc = m.check(ctx, terms, "eccx_bls_aggregate_verify: the offsets decrease")) return rc;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (terms) {
+    if (int rc = m.grow_slots(ctx, terms)) return rc;
+  }
+  const BlsWhat& w = *bls_what(opts);
+  uint8_t *d_go = nullptr, *d_keys = nullptr, *d_sg = nullptr, *d_v = nullptr;
+  int rc = grow(ctx, B_IO + IO_A, (n + 1) * sizeof(uint64_t), &d_go);
+  if (!rc && terms) rc = grow(ctx, B_IO + IO_B, terms * w.key_enc, &d_keys);
+  if (!rc) rc = grow(ctx, B_IO + IO_P, n * w.sig_enc, &d_sg);
+  if (!rc) rc = grow(ctx, B_IO + IO_F, n, &d_v);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  HIP_TRY(ctx, settled(hipMemcpyAsync(d_go, group_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s)));
+  HIP_TRY(ctx, settled(hipMemcpyAsync(d_sg, sigs, n * w.sig_enc, hipMemcpyHostToDevice, s)));
+  if (terms) {
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_keys, pubkeys, terms * w.key_enc, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(m.copy_in(0, terms, s)));
+  }
+  rc = bls_aggregate_verify_dev(ctx, n, terms ? m.dev_msgs(0) : nullptr, terms ? m.dev_offsets(0) : nullptr, dst, dst_len, d_sg, d_keys,
+                                d_go, terms, d_v, opts, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  HIP_TRY(ctx, settled(hipMemcpyAsync(verdicts, d_v, n, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
 }
 
 size_t eccx_pairing_lanes(const eccx_ctx* ctx) {

@@ -42,6 +42,20 @@ hipError_t launch_bls_fold(hipStream_t s, size_t n, const uint8_t* pairing_verdi
   hipLaunchKernelGGL(k_bls_fold, dim3(byte_grid(n)), dim3(WG), 0, s, n, pairing_verdicts, verdicts);
   return hipGetLastError();
 }
+hipError_t launch_bls_group_flags(hipStream_t s, size_t n, size_t terms, const uint64_t* group_offsets, const uint8_t* key_fl,
+                                  const uint8_t* h_fl, uint32_t* pre) {
+  if (terms == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_bls_group_flags, dim3(byte_grid(terms)), dim3(WG), 0, s, n, terms, group_offsets, key_fl, h_fl, pre);
+  return hipGetLastError();
+}
+hipError_t launch_bls_assemble_groups(hipStream_t s, size_t n, size_t terms, int min_sig, const uint8_t* key_xy, const uint8_t* key_fl,
+                                      const uint8_t* sig_xy, const uint8_t* sig_fl, const uint8_t* h_xy, const uint8_t* h_fl,
+                                      const uint64_t* group_offsets, const uint32_t* pre, uint8_t* g1, uint8_t* g1_inf, uint8_t* g2,
+                                      uint8_t* g2_inf, uint64_t* term_offsets, uint8_t* verdicts) {
+  hipLaunchKernelGGL(k_bls_assemble_groups, dim3(byte_grid(terms + n)), dim3(WG), 0, s, n, terms, min_sig, key_xy, key_fl, sig_xy, sig_fl,
+                     h_xy, h_fl, group_offsets, pre, g1, g1_inf, g2, g2_inf, term_offsets, verdicts);
+  return hipGetLastError();
+}
 
 void point_sum_ops_BLS12_381(CurveOps& t) { t.point_sum = point_sum_<G1>; }
 void point_sum_ops_BLS12_381_G2(CurveOps& t) { t.point_sum = point_sum_<G2>; }

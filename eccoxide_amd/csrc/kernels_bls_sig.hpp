@@ -290,4 +290,87 @@ __global__ void __launch_bounds__(WG) k_bls_fold(size_t n, const uint8_t* __rest
   if (i < n && verdicts[i] == 0) verdicts[i] = pairing_verdicts[i] == 1 ? BLS_VALID : BLS_INVALID;
 }
 
+// ---- AggregateVerify: unit i has signature i and the (key, message) pairs group_offsets[i] .. group_offsets[i + 1] -----------
+// The unit that owns pair t, by a binary search over the n + 1 offsets (they increase wherever every range is valid), and
+// whether t lies in that unit's valid range: a pair outside every valid range belongs to no unit.
+ECCX_DEV bool bls_unit_of(const uint64_t* __restrict__ go, size_t n, size_t terms, uint64_t t, size_t& unit) {
+  const uint64_t first = go[0];
+  size_t lo = 0, hi = n;  // the first index in 1 .. n whose offset exceeds t lies in (lo, hi]
+  while (hi - lo > 1) {
+    const size_t mid = lo + (hi - lo) / 2;
+    if (go[mid] - first > t) hi = mid;
+    else lo = mid;
+  }
+  unit = lo;
+  uint64_t a, len;
+  return psum_range(go, first, lo, terms, a, len) && t >= a && t - a < len;
+}
+enum : uint32_t { BLS_PRE_MSG = 1u, BLS_PRE_KEY = 2u };
+// one lane per pair: what its flags decide goes into its unit's word of `pre` (zeroed before): a message whose offsets
+// decrease (the hash's flag 2), a key that fails KeyValidate (k_bls_key_flags left 2).  No lane's work grows with a group.
+__global__ void __launch_bounds__(WG) k_bls_group_flags(size_t n, size_t terms, const uint64_t* __restrict__ go,
+                                                        const uint8_t* __restrict__ key_fl, const uint8_t* __restrict__ h_fl, uint32_t* pre) {
+  const size_t t = (size_t)blockIdx.x * WG + threadIdx.x;
+  if (t >= terms) return;
+  const uint32_t bits = (h_fl[t] == 2 ? BLS_PRE_MSG : 0u) | (key_fl[t] != 0 ? BLS_PRE_KEY : 0u);
+  size_t u;
+  if (bits && bls_unit_of(go, n, terms, t, u)) atomicOr(pre + u, bits);
+}
+// Lanes 0 .. terms: pair t of unit u goes to flat position t + u (= group_offsets[u] + u + j): (pk, H(m)) for min-pk,
+// (H(m), pk) for min-sig.  Lanes terms .. terms + n: unit i's last term at position group_offsets[i + 1] + i, the signature
+// against the negated generator, the unit's term offset group_offsets[i] + i (lane 0 of them also writes the last one),
+// and the verdict the flags already decide (0: the equation decides, k_bls_fold).  A decided unit's terms are all flagged
+// infinite.  g1: (terms + n) x 96, g2: (terms + n) x 192, one flag byte each per position.
+__global__ void __launch_bounds__(WG) k_bls_assemble_groups(size_t n, size_t terms, int min_sig, const uint8_t* __restrict__ key_xy,
+                                                            const uint8_t* __restrict__ key_fl, const uint8_t* __restrict__ sig_xy,
+                                                            const uint8_t* __restrict__ sig_fl, const uint8_t* __restrict__ h_xy,
+                                                            const uint8_t* __restrict__ h_fl, const uint64_t* __restrict__ go,
+                                                            const uint32_t* __restrict__ pre, uint8_t* __restrict__ g1,
+                                                            uint8_t* __restrict__ g1_inf, uint8_t* __restrict__ g2,
+                                                            uint8_t* __restrict__ g2_inf, uint64_t* __restrict__ term_offsets,
+                                                            uint8_t* __restrict__ verdicts) {
+  const size_t x = (size_t)blockIdx.x * WG + threadIdx.x;
+  if (x >= terms + n) return;
+  const size_t kb = min_sig ? 192 : 96, hb = min_sig ? 96 : 192;  // the key's and H(m)'s (= the signature's) record
+  if (x < terms) {
+    size_t u;
+    if (!bls_unit_of(go, n, terms, x, u)) return;
+    const bool dead = pre[u] != 0 || sig_fl[u] == 2;
+    // either point at infinity makes the term contribute 1 (a key flagged at all has made the unit dead)
+    const uint8_t inf = (dead || key_fl[x] != 0 || h_fl[x] == 1) ? 1 : 0;
+    const size_t pos = x + u;
+    uint8_t* kd = (min_sig ? g2 : g1) + pos * kb;
+    uint8_t* hd = (min_sig ? g1 : g2) + pos * hb;
+    for (size_t k = 0; k < kb; ++k) kd[k] = key_xy[x * kb + k];
+    for (size_t k = 0; k < hb; ++k) hd[k] = h_xy[x * hb + k];
+    g1_inf[pos] = g2_inf[pos] = inf;
+    return;
+  }
+  const size_t i = x - terms;
+  const uint64_t first = go[0];
+  uint64_t lo, len;
+  const bool range_ok = psum_range(go, first, i, terms, lo, len);
+  const uint32_t p = pre[i];
+  uint8_t v = 0;
+  if (sig_fl[i] == 2 || !range_ok || (p & BLS_PRE_MSG)) v = BLS_MALFORMED;
+  else if (len == 0 || (p & BLS_PRE_KEY)) v = BLS_BAD_KEY;
+  term_offsets[i] = go[i] - first + i;
+  if (i == 0) term_offsets[n] = go[n] - first + n;
+  if (range_ok) {
+    const size_t pos = (size_t)(lo + len) + i;
+    const uint8_t inf = (v != 0 || sig_fl[i] == 1) ? 1 : 0;
+    uint8_t* a = g1 + pos * 96;
+    uint8_t* b = g2 + pos * 192;
+    if (min_sig) {
+      for (int k = 0; k < 96; ++k) a[k] = sig_xy[i * 96 + k];
+      for (int k = 0; k < 192; ++k) b[k] = BLS_NEG_G2[k];
+    } else {
+      for (int k = 0; k < 96; ++k) a[k] = BLS_NEG_G1[k];
+      for (int k = 0; k < 192; ++k) b[k] = sig_xy[i * 192 + k];
+    }
+    g1_inf[pos] = g2_inf[pos] = inf;
+  }
+  verdicts[i] = v;
+}
+
 }  // namespace eccx

@@ -185,6 +185,20 @@ struct CurveOps {
   int (*pairing_miller_grid)(int cus, size_t n);
   int (*pairing_finalexp_grid)(int cus, size_t n);
   int pairing_row_words, pairing_slab_words;
+  // Products of pairings over RAGGED groups (kernels_pairing_groups.hpp): group g is terms offsets[g] - offsets[0] ..
+  // offsets[g + 1] - offsets[0] of `terms` flat records.  pairing_groups enqueues the scan of the groups' chunk counts, the
+  // per-term prepare, the Miller loop of one chunk (at most pairing_group_chunk terms) per lane over `slots` = n + terms /
+  // pairing_group_chunk chunk slots, the passes of the segmented Fp12 product (at most pairing_group_fanin values per lane
+  // and pass) and the gather of one value per group into fbuf, for pairing_finalexp; status takes 0 / 2 (a rejected point
+  // under OPT_VALIDATE, or a range that decreases or leaves the records: such a group reads nothing).  tbuf: ceil(terms /
+  // WG) rows, cbuf: ceil(slots / WG) rows, fbuf: ceil(n / WG) rows of pairing_row_words x WG words; cstart: n + 1 words;
+  // tflag: `terms` bytes; slab: pairing_slab_words x WG words per workgroup of pairing_groups_grid(cus, slots).  Every size
+  // and launch is a function of (n, terms) alone; nothing is read back.
+  hipError_t (*pairing_groups)(hipStream_t s, int cus, size_t n, size_t terms, const uint64_t* offsets, const uint8_t* g1,
+                               const uint8_t* g1_inf, const uint8_t* g2, const uint8_t* g2_inf, uint32_t* tbuf, uint32_t* cbuf,
+                               uint32_t* fbuf, uint32_t* cstart, uint8_t* tflag, uint8_t* status, uint32_t* slab, uint32_t opts);
+  int (*pairing_groups_grid)(int cus, size_t slots);
+  int pairing_group_chunk, pairing_group_fanin;
   // 1: the C ABI refuses the options this curve has no kernel for (ECCX_TABLE_IN_LDS, ECCX_CT_GATHER, ECCX_ASSUME_SUBGROUP)
   // with ECCX_ERR_ARG; 0 (every curve before jubjub): such options fall back to a kernel that returns the same bytes
   int strict_opts;
@@ -254,6 +268,17 @@ hipError_t launch_bls_assemble(hipStream_t s, size_t n, int min_sig, const uint8
                                const uint8_t* sig_fl, const uint8_t* h_xy, const uint8_t* h_fl, const uint64_t* key_offsets, size_t keys,
                                uint8_t* g1, uint8_t* g1_inf, uint8_t* g2, uint8_t* g2_inf, uint8_t* verdicts);
 hipError_t launch_bls_fold(hipStream_t s, size_t n, const uint8_t* pairing_verdicts, uint8_t* verdicts);
+// AggregateVerify: unit i has signature i and the (key, message) pairs group_offsets[i] .. group_offsets[i + 1] of `terms`.
+// launch_bls_group_flags ORs what each pair's flags decide into its unit's word of `pre` (zeroed by the caller on the
+// stream: bit 0 a message whose offsets decrease, bit 1 a key that fails KeyValidate); launch_bls_assemble_groups writes unit
+// i's L_i + 1 terms at flat positions group_offsets[i] - group_offsets[0] + i + j, the last being the signature against the
+// negated generator, the n + 1 term offsets of the ragged pairing product, and the verdicts the flags already decide.
+hipError_t launch_bls_group_flags(hipStream_t s, size_t n, size_t terms, const uint64_t* group_offsets, const uint8_t* key_fl,
+                                  const uint8_t* h_fl, uint32_t* pre);
+hipError_t launch_bls_assemble_groups(hipStream_t s, size_t n, size_t terms, int min_sig, const uint8_t* key_xy, const uint8_t* key_fl,
+                                      const uint8_t* sig_xy, const uint8_t* sig_fl, const uint8_t* h_xy, const uint8_t* h_fl,
+                                      const uint64_t* group_offsets, const uint32_t* pre, uint8_t* g1, uint8_t* g1_inf, uint8_t* g2,
+                                      uint8_t* g2_inf, uint64_t* term_offsets, uint8_t* verdicts);
 
 constexpr int LAUNCH_WG = 256;
 

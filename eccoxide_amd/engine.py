@@ -44,6 +44,8 @@ PREP_PAIRING = 4096
 PREP_X448 = 8192
 PREP_MSM = 16384
 PREP_BLS = 32768
+PREP_PAIRING_GROUPS = 65536
+PREP_BLS_AGGREGATE = 131072
 PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
@@ -169,7 +171,8 @@ class Engine:
 
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
-                h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False, bls: bool = False):
+                h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False, bls: bool = False,
+                pairing_groups: bool = False, bls_aggregate: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
@@ -178,7 +181,10 @@ class Engine:
         slab and rows of pairing / pairing_check (curve "bls12_381_g2") for every shape with n * max(pairs, 1) <= max_n;
         x448: the row buffer of x448 / x448_t (any curve: X448 has no id of its own) and, with host, its host-buffer copies;
         msm: the workspace of msm / msm_t (curve "bls12_381_g1") for every n <= max_n; bls: the slab of the bls_* calls
-        (curve "bls12_381_g2") and what their parts need on both curves, for max(n, keys) <= max_n."""
+        (curve "bls12_381_g2") and what their parts need on both curves, for max(n, keys) <= max_n; pairing_groups: the
+        slab and rows of pairing_groups / pairing_check_groups (curve "bls12_381_g2") for every shape with n + terms <=
+        max_n; bls_aggregate: the slab of bls_aggregate_verify (curve "bls12_381_g2") and what its parts need, for n + terms
+        <= max_n."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
@@ -186,7 +192,9 @@ class Engine:
                                            | (PREP_ED25519_SIGN if ed25519_sign else 0)
                                            | (PREP_ECDSA_SIGN if ecdsa_sign else 0) | (PREP_H2C if h2c else 0)
                                            | (PREP_PAIRING if pairing else 0) | (PREP_X448 if x448 else 0)
-                                           | (PREP_MSM if msm else 0) | (PREP_BLS if bls else 0)))
+                                           | (PREP_MSM if msm else 0) | (PREP_BLS if bls else 0)
+                                           | (PREP_PAIRING_GROUPS if pairing_groups else 0)
+                                           | (PREP_BLS_AGGREGATE if bls_aggregate else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -498,6 +506,62 @@ class Engine:
                                                                  BLS_MIN_SIG if min_sig else 0, stream))
         return verdicts
 
+    def bls_aggregate_verify(self, messages, sigs: bytes, pubkeys: bytes, groups, dst: bytes, *, min_sig: bool = False,
+                             require_distinct: bool = False) -> bytes:
+        """AggregateVerify (the draft's CoreAggregateVerify): unit i has one aggregate signature and groups[i] (key, message)
+        pairs of the flat arrays `pubkeys` and `messages`, e(sig, -G) prod e(pk_j, H(m_j)) = 1.  MALFORMED (the signature)
+        before BAD_KEY (any key fails KeyValidate; the EMPTY group) before the equation.  Distinctness of a unit's messages
+        is not checked on the device; require_distinct turns a SIG_VALID unit with a repeated message into SIG_INVALID here on
+        the host, which is the basic scheme (the augmentation and proof-of-possession schemes do not need it)."""
+        import numpy as np
+
+        sizes = [int(g) for g in groups]
+        if any(g < 0 for g in sizes):
+            raise ValueError("group sizes must not be negative")
+        n, terms = len(sizes), len(messages)
+        kb, sb = self._bls_sizes(min_sig)
+        group_offsets = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(sizes, out=group_offsets[1:])
+        if int(group_offsets[-1]) != terms or len(sigs) != n * sb or len(pubkeys) != terms * kb:
+            raise ValueError(f"one message and one key of {kb} bytes per pair (sum(groups) of them), sigs n x {sb} bytes")
+        msgs, offsets = self._ragged(messages)
+        dst = bytes(dst)
+        verdicts = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_bls_aggregate_verify(self._ctx, n, msgs if msgs else None, offsets.ctypes.data,
+                                                        dst if dst else None, len(dst), sigs, pubkeys if terms else None,
+                                                        group_offsets.ctypes.data, terms, verdicts, BLS_MIN_SIG if min_sig else 0))
+        out = bytearray(verdicts.raw[:n])
+        if require_distinct:
+            for i in range(n):
+                lo, hi = int(group_offsets[i]), int(group_offsets[i + 1])
+                if out[i] == SIG_VALID and len({bytes(m) for m in messages[lo:hi]}) != hi - lo:
+                    out[i] = SIG_INVALID
+        return bytes(out)
+
+    def bls_aggregate_verify_t(self, msgs, offsets, sigs, pubkeys, group_offsets, dst: bytes, verdicts=None, *,
+                               min_sig: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of bls_aggregate_verify (eccx_bls_aggregate_verify_dev): msgs and offsets (terms + 1 entries) hold
+        one message per pair, pubkeys one key per pair, group_offsets a contiguous int64 CUDA tensor of n + 1 entries into
+        the pairs.  A range that decreases or leaves the pairs, and a message whose offsets decrease, make their unit
+        SIG_MALFORMED.  Distinctness of the messages is the caller's to check."""
+        import torch
+
+        terms, msgs = self._bls_msgs_t(msgs, offsets)
+        kb, sb = self._bls_sizes(min_sig)
+        if group_offsets.dtype not in (torch.int64, torch.uint64) or group_offsets.numel() < 1 or not group_offsets.is_contiguous() \
+                or not group_offsets.is_cuda or group_offsets.device.index != self.device:
+            raise ValueError("group_offsets must be a contiguous int64 CUDA tensor of n + 1 entries on this engine's GPU")
+        n = group_offsets.numel() - 1
+        verdicts = torch.empty((n,), dtype=torch.uint8, device=offsets.device) if verdicts is None else verdicts
+        self._tensors(terms, ("pubkeys", pubkeys, kb))
+        stream = self._bls_t(n, (("sigs", sigs, sb), ("verdicts", verdicts, 1)), stream, offsets)
+        dst = bytes(dst)
+        self._check(self._lib.eccx_bls_aggregate_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None,
+                                                            len(dst), sigs.data_ptr(), pubkeys.data_ptr() if terms else None,
+                                                            group_offsets.data_ptr(), terms, verdicts.data_ptr(),
+                                                            BLS_MIN_SIG if min_sig else 0, stream))
+        return verdicts
+
     def msm_window_bits(self, n: int) -> int:
         """The window width msm uses for n terms (a pure function of n)."""
         return int(self._lib.eccx_msm_window_bits(int(n)))
@@ -805,6 +869,91 @@ class Engine:
         else:
             self._check(self._lib.eccx_pairing_check_dev(self._ctx, n, pairs, ptr(g1), ptr(g1_inf), ptr(g2), ptr(g2_inf),
                                                          status.data_ptr(), opts, stream))
+        return out, status
+
+    # ---- products of pairings over ragged groups (eccx_pairing_groups, eccx_pairing_check_groups) -----------------------
+    def pairing_group_chunk(self) -> int:
+        """K: the terms of one lane's Miller loop in pairing_groups."""
+        return int(self._lib.eccx_pairing_group_chunk())
+
+    def pairing_group_fanin(self) -> int:
+        """R: the chunk values one lane multiplies in a pass of pairing_groups' segmented product."""
+        return int(self._lib.eccx_pairing_group_fanin())
+
+    def _pairing_groups_host(self, want_value, g1, g2, groups, g1_inf, g2_inf, validate):
+        import numpy as np
+
+        sizes = [int(g) for g in groups]
+        if any(g < 0 for g in sizes):
+            raise ValueError("group sizes must not be negative")
+        n = len(sizes)
+        term_offsets = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(sizes, out=term_offsets[1:])
+        terms = int(term_offsets[-1])
+        if len(g1) != 96 * terms or len(g2) != 192 * terms:
+            raise ValueError("g1 must be sum(groups) x 96 bytes and g2 sum(groups) x 192")
+        for name, f in (("g1_inf", g1_inf), ("g2_inf", g2_inf)):
+            if f is not None and len(f) != terms:
+                raise ValueError(f"{name}: expected {terms} flag bytes, got {len(f)}")
+        out = ctypes.create_string_buffer(max(1, 576 * n))
+        status = ctypes.create_string_buffer(max(1, n))
+        opts = VALIDATE_POINTS if validate else 0
+        a = (self._ctx, n, terms, g1 if terms else None, g1_inf if terms else None, g2 if terms else None,
+             g2_inf if terms else None, term_offsets.ctypes.data)
+        if want_value:
+            self._check(self._lib.eccx_pairing_groups(*a, out, status, opts))
+        else:
+            self._check(self._lib.eccx_pairing_check_groups(*a, status, opts))
+        return out.raw[:576 * n], status.raw[:n]
+
+    def pairing_groups(self, g1: bytes, g2: bytes, groups, *, g1_inf: Optional[bytes] = None, g2_inf: Optional[bytes] = None,
+                       validate: bool = False):
+        """One product of pairings per RAGGED group (eccx_pairing_groups): g1 (96 bytes) and g2 (192 bytes) hold the records
+        of all groups back to back, groups the number of terms in each, as bls_fast_aggregate_verify takes its groups.  The
+        empty group gives 1; a flagged term contributes 1.  Returns (values n x 576, flags n)."""
+        return self._pairing_groups_host(True, g1, g2, groups, g1_inf, g2_inf, validate)
+
+    def pairing_check_groups(self, g1: bytes, g2: bytes, groups, *, g1_inf: Optional[bytes] = None,
+                             g2_inf: Optional[bytes] = None, validate: bool = False) -> bytes:
+        """Whether each ragged group's product is 1, compared on the device (eccx_pairing_check_groups): n PAIRING_* bytes."""
+        return self._pairing_groups_host(False, g1, g2, groups, g1_inf, g2_inf, validate)[1]
+
+    def pairing_groups_t(self, g1, g2, term_offsets, out=None, flags=None, *, g1_inf=None, g2_inf=None, validate: bool = False,
+                         stream: Optional[int] = None):
+        """Device-tensor form of pairing_groups (eccx_pairing_groups_dev): term_offsets a contiguous int64 CUDA tensor of
+        n + 1 entries into the flat records.  The offsets are not read back: a group whose range decreases or leaves the
+        records is rejected alone.  Returns (values n x 576, flags n) tensors."""
+        return self._pairing_groups_t(True, g1, g2, term_offsets, out, flags, g1_inf, g2_inf, validate, stream)
+
+    def pairing_check_groups_t(self, g1, g2, term_offsets, verdicts=None, *, g1_inf=None, g2_inf=None, validate: bool = False,
+                               stream: Optional[int] = None):
+        """Device-tensor form of pairing_check_groups (eccx_pairing_check_groups_dev); returns the n verdict bytes."""
+        return self._pairing_groups_t(False, g1, g2, term_offsets, None, verdicts, g1_inf, g2_inf, validate, stream)[1]
+
+    def _pairing_groups_t(self, want_value, g1, g2, term_offsets, out, status, g1_inf, g2_inf, validate, stream):
+        import torch
+
+        if term_offsets.dtype not in (torch.int64, torch.uint64) or term_offsets.numel() < 1 or not term_offsets.is_contiguous() \
+                or not term_offsets.is_cuda or term_offsets.device.index != self.device:
+            raise ValueError("term_offsets must be a contiguous int64 CUDA tensor of n + 1 entries on this engine's GPU")
+        n = term_offsets.numel() - 1
+        terms = self._units(g1, 96, "g1")
+        self._tensors(terms, ("g1", g1, 96), ("g2", g2, 192), ("g1_inf", g1_inf, 1), ("g2_inf", g2_inf, 1))
+        dev = torch.device("cuda", self.device)
+        if want_value and out is None:
+            out = torch.empty((n, 576), dtype=torch.uint8, device=dev)
+        if status is None:
+            status = torch.empty((n,), dtype=torch.uint8, device=dev)
+        self._tensors(n, ("out", out, 576), ("flags", status, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: t.data_ptr() if (t is not None and terms) else None
+        opts = VALIDATE_POINTS if validate else 0
+        a = (self._ctx, n, terms, ptr(g1), ptr(g1_inf), ptr(g2), ptr(g2_inf), term_offsets.data_ptr())
+        if want_value:
+            self._check(self._lib.eccx_pairing_groups_dev(*a, out.data_ptr(), status.data_ptr(), opts, stream))
+        else:
+            self._check(self._lib.eccx_pairing_check_groups_dev(*a, status.data_ptr(), opts, stream))
         return out, status
 
     def _hash_to(self, fn, width, messages, dst, nonuniform):

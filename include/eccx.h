@@ -32,6 +32,8 @@
  *                              :501-529; clear_cofactor g2.rs:161-171
  *   eccx_pairing[_dev], eccx_pairing_check[_dev]  pairing, multi_miller_loop(..).final_exponentiation()
  *                              src/curve/bls12_381/pairing.rs:166-197, 263-272, 334, 360, 616-626
+ *   eccx_pairing_groups[_dev], eccx_pairing_check_groups[_dev]  the same over ragged groups of terms (one
+ *                              multi_miller_loop per group, cut into chunks of K terms; no counterpart in the reference)
  *   eccx_x25519[_dev]          MontgomeryPoint ladder / x25519   curve25519.rs:474-541, src/protocol/x25519.rs:14-51
  *   eccx_x448[_dev]            MontgomeryPoint ladder / x448     src/curve/curve448.rs:263-330, src/protocol/x448.rs:16-49
  *   eccx_point_compress[_dev]  PointAffine::compress, to_compressed, to_uncompressed, encode_point
@@ -281,6 +283,12 @@ enum {
   ECCX_PREP_BLS = 1u << 15,     /* eccx_reserve (bls12_381_g2): the working slab of the eccx_bls_* entry points for max(n, keys) <=
                                    max_n, and with it what the hash, the pairing (pairs = 2), the decoders, the group sum and the
                                    secret-scalar ladders need on both curves (the comb tables are eccx_prepare's) */
+  ECCX_PREP_PAIRING_GROUPS = 1u << 16, /* eccx_reserve (bls12_381_g2): the slab and the rows of eccx_pairing_groups /
+                                   eccx_pairing_check_groups for every shape with n + terms <= max_n: 672 bytes per group,
+                                   per term and per chunk slot (n + terms / K), 4 bytes per group and 1 per term */
+  ECCX_PREP_BLS_AGGREGATE = 1u << 17, /* eccx_reserve (bls12_381_g2): the working slab of eccx_bls_aggregate_verify for n +
+                                   terms <= max_n (a slab of its own: ECCX_PREP_BLS reserves what it did before), and with it
+                                   what the decoders, the hash and the ragged pairing product need */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -585,6 +593,42 @@ int eccx_pairing_check_dev(eccx_ctx* ctx, size_t n, size_t pairs, const void* d_
  * units takes the kernels' grid-stride path.  0 for a null context. */
 size_t eccx_pairing_lanes(const eccx_ctx* ctx);
 
+/* Products of pairings over RAGGED groups: group g is the product of e(P_t, Q_t) over the terms term_offsets[g] ..
+ * term_offsets[g + 1] (relative to term_offsets[0], as every offsets array of this ABI) of flat arrays of `terms` records,
+ * the same records and flags as eccx_pairing takes: what AggregateVerify (one signature against k (key, message) pairs)
+ * and any batch with groups of different lengths need, without padding every group to the longest.  With
+ * term_offsets[g] = g * pairs the output is byte for byte that of eccx_pairing(.., pairs).
+ *   g1, g2  : terms x 96 and terms x 192; g1_inf, g2_inf: `terms` flag bytes or NULL; a flagged term contributes 1
+ *   out     : n x 576; flags: n bytes (0, or ECCX_FLAG_REJECTED with zero bytes); verdicts: n x ECCX_PAIRING_*
+ *   opts    : 0 or ECCX_VALIDATE_POINTS: a bad finite point rejects its group and no other
+ * The empty group is the empty product (value 1, ECCX_PAIRING_ONE).  A group of L terms is cut into ceil(L / K) chunks of at
+ * most K = eccx_pairing_group_chunk() consecutive terms (of even size: 9 terms are 5 + 4); one lane runs the shared-squaring Miller loop of one chunk, and the
+ * chunk values of a group are multiplied down in passes in which a lane multiplies at most R = eccx_pairing_group_fanin()
+ * neighbours.  No lane's work grows with a group's length beyond K Miller terms, R products per pass and logarithmic
+ * searches: one group of 2^20 terms and 2^20 groups of one term are equally legal.  The chunk map is computed on the device
+ * (a scan and a search); every buffer size and launch count is a function of (n, terms) alone and nothing is read back.
+ * The host forms return ECCX_ERR_ARG for a null buffer, for offsets that decrease, for a last offset beyond `terms` and
+ * for n + terms above 2^31, with nothing written.  The _dev forms cannot read the offsets: a group whose range decreases or
+ * leaves `terms` is rejected alone (ECCX_FLAG_REJECTED / ECCX_PAIRING_REJECTED), nothing of it is read and its neighbours
+ * stand, as in eccx_point_sum_dev.  Two groups cannot share a term: behind a decreasing offset, a group that starts before
+ * the end of an earlier range (one that neither decreases nor leaves `terms`) is rejected as well.  n == 0 returns ECCX_OK.
+ * The _dev forms
+ * enqueue on `stream` without synchronising; after eccx_reserve(ctx, ECCX_BLS12_381_G2, max_n, ECCX_PREP_PAIRING_GROUPS) a
+ * _dev call with n + terms <= max_n neither allocates, frees nor synchronises. */
+int eccx_pairing_groups(eccx_ctx* ctx, size_t n, size_t terms, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                        const uint8_t* g2_inf, const uint64_t* term_offsets, uint8_t* out, uint8_t* flags, uint32_t opts);
+int eccx_pairing_groups_dev(eccx_ctx* ctx, size_t n, size_t terms, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                            const void* d_g2_inf, const void* d_term_offsets, void* d_out, void* d_flags, uint32_t opts,
+                            void* stream);
+int eccx_pairing_check_groups(eccx_ctx* ctx, size_t n, size_t terms, const uint8_t* g1, const uint8_t* g1_inf, const uint8_t* g2,
+                              const uint8_t* g2_inf, const uint64_t* term_offsets, uint8_t* verdicts, uint32_t opts);
+int eccx_pairing_check_groups_dev(eccx_ctx* ctx, size_t n, size_t terms, const void* d_g1, const void* d_g1_inf, const void* d_g2,
+                                  const void* d_g2_inf, const void* d_term_offsets, void* d_verdicts, uint32_t opts,
+                                  void* stream);
+/* K: the terms of one lane's Miller loop; R: the values one lane multiplies in a pass of the segmented product */
+int eccx_pairing_group_chunk(void);
+int eccx_pairing_group_fanin(void);
+
 /* Multi-scalar multiplication: ONE result sum_i k_i * P_i from n terms, by the bucket method (Pippenger) with signed
  * windows: what a KZG commitment, an aggregation of public keys with coefficients and batch verification by a random
  * linear combination compute.  Every other entry point computes n results, one per lane; here the lanes cooperate.
@@ -699,6 +743,34 @@ int eccx_bls_fast_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs,
 int eccx_bls_fast_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
                                        size_t dst_len, const void* d_sigs, const void* d_pubkeys, const void* d_key_offsets,
                                        size_t keys, void* d_verdicts, uint32_t opts, void* stream);
+
+/* AggregateVerify: ONE aggregate signature against k (key, message) pairs with DIFFERENT messages,
+ * e(sig, -G) * prod_j e(pk_j, H(m_j)) = 1 -- the draft's CoreAggregateVerify.  Unit i has signature i and the pairs
+ * group_offsets[i] .. group_offsets[i + 1] (relative to group_offsets[0]) of flat arrays of `terms` keys and `terms` ragged
+ * messages (offsets: terms + 1 values).  Variants, tag and encodings as for eccx_bls_verify.  On the one stream: the key
+ * decoder with its subgroup test over all `terms` keys and KeyValidate on its flags, the signature decoder over n, the hash
+ * over `terms` messages, an assembly kernel that writes unit i's L_i + 1 terms at flat positions group_offsets[i] + i + j
+ * (the last is the signature against the negated generator) with their term offsets, eccx_pairing_check_groups' kernels,
+ * and the fold onto ECCX_SIG_*.
+ *   ECCX_SIG_MALFORMED  the signature does not decode or is outside the subgroup; the unit's range decreases or leaves
+ *                       `terms`; a message of the unit has decreasing offsets
+ *   ECCX_SIG_BAD_KEY    any key of the unit fails KeyValidate, the identity included; the EMPTY group, which the draft makes
+ *                       a precondition (the choice of eccx_bls_fast_aggregate_verify)
+ * MALFORMED before BAD_KEY before the equation.  A decided unit's terms are flagged infinite: the pairing runs on nothing of
+ * it.  The identity signature and an H(m) at infinity are legal terms.
+ * DISTINCTNESS OF THE MESSAGES IS NOT CHECKED: the basic scheme's AggregateVerify requires the messages of a unit to be
+ * pairwise distinct and its caller owes that check; the message-augmentation and proof-of-possession schemes do not need
+ * it.  The host form returns ECCX_ERR_ARG for null buffers, decreasing message or group offsets and a last group offset
+ * beyond `terms`; the _dev form answers those per unit as above.  (Units whose ranges overlap, possible only around a
+ * decreasing group offset, share flat positions: their verdicts are then unspecified.)  n == 0 returns ECCX_OK.  After
+ * eccx_reserve(ctx, ECCX_BLS12_381_G2, max_n, ECCX_PREP_BLS_AGGREGATE) a _dev call with n + terms <= max_n neither allocates,
+ * frees nor synchronises. */
+int eccx_bls_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                              size_t dst_len, const uint8_t* sigs, const uint8_t* pubkeys, const uint64_t* group_offsets,
+                              size_t terms, uint8_t* verdicts, uint32_t opts);
+int eccx_bls_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
+                                  size_t dst_len, const void* d_sigs, const void* d_pubkeys, const void* d_group_offsets,
+                                  size_t terms, void* d_verdicts, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

@@ -57,20 +57,20 @@ pub fn point_sum(gpu: &GpuContext, group: Group, offsets: &[u64], points: &[u8],
 
 /// Sizes that do not fit are refused here, as the library refuses them (`ECCX_ERR_ARG`): every pointer handed over below is
 /// read for the full length its count implies.
-fn size_err(what: &str) -> GpuError {
+pub(crate) fn size_err(what: &str) -> GpuError {
     GpuError { code: ffi::ECCX_ERR_ARG, message: String::from(what) }
 }
 
 /// (key bytes, signature bytes) of the variant
-fn sizes_of(min_sig: bool) -> (usize, usize) {
+pub(crate) fn sizes_of(min_sig: bool) -> (usize, usize) {
     if min_sig { (96, 48) } else { (48, 96) }
 }
 
-fn variant(min_sig: bool) -> u32 {
+pub(crate) fn variant(min_sig: bool) -> u32 {
     if min_sig { ffi::ECCX_BLS_MIN_SIG } else { 0 }
 }
 
-fn ragged(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+pub(crate) fn ragged(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
     let (mut bytes, mut offsets) = (Vec::new(), vec![0u64]);
     for m in msgs {
         bytes.extend_from_slice(m);

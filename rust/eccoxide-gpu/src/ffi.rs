@@ -67,6 +67,8 @@ pub const ECCX_PREP_PAIRING: u32 = 1 << 12; // eccx_pairing's / eccx_pairing_che
 pub const ECCX_PREP_X448: u32 = 1 << 13; // eccx_x448's result rows (any curve id) and, with ECCX_PREP_HOST, its copies
 pub const ECCX_PREP_BLS: u32 = 1 << 15; // the working slab of the eccx_bls_* entry points (bls12_381_g2)
 pub const ECCX_PREP_MSM: u32 = 1 << 14; // eccx_msm's workspace for every n <= max_n (bls12_381_g1)
+pub const ECCX_PREP_PAIRING_GROUPS: u32 = 1 << 16; // eccx_pairing_groups' slab and rows for n + terms <= max_n (bls12_381_g2)
+pub const ECCX_PREP_BLS_AGGREGATE: u32 = 1 << 17; // eccx_bls_aggregate_verify's slab for n + terms <= max_n (bls12_381_g2)
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -186,6 +188,20 @@ extern "C" {
                                   stream: *mut c_void) -> c_int;
     pub fn eccx_pairing_lanes(ctx: *const eccx_ctx) -> usize;
 
+    // products of pairings over ragged groups: group g is the terms term_offsets[g] .. term_offsets[g + 1]
+    pub fn eccx_pairing_groups(ctx: *mut eccx_ctx, n: usize, terms: usize, g1: *const u8, g1_inf: *const u8, g2: *const u8,
+                               g2_inf: *const u8, term_offsets: *const u64, out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_pairing_groups_dev(ctx: *mut eccx_ctx, n: usize, terms: usize, d_g1: *const c_void, d_g1_inf: *const c_void,
+                                   d_g2: *const c_void, d_g2_inf: *const c_void, d_term_offsets: *const c_void, d_out: *mut c_void,
+                                   d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_pairing_check_groups(ctx: *mut eccx_ctx, n: usize, terms: usize, g1: *const u8, g1_inf: *const u8, g2: *const u8,
+                                     g2_inf: *const u8, term_offsets: *const u64, verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_pairing_check_groups_dev(ctx: *mut eccx_ctx, n: usize, terms: usize, d_g1: *const c_void, d_g1_inf: *const c_void,
+                                         d_g2: *const c_void, d_g2_inf: *const c_void, d_term_offsets: *const c_void,
+                                         d_verdicts: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_pairing_group_chunk() -> c_int;
+    pub fn eccx_pairing_group_fanin() -> c_int;
+
     // ONE result sum_i scalars[i] * points[i] on BLS12-381 G1, by the bucket method (public scalars only)
     pub fn eccx_msm(ctx: *mut eccx_ctx, curve: c_int, n: usize, scalars: *const u8, points: *const u8, inf: *const u8,
                     out: *mut u8, flag: *mut u8, opts: u32) -> c_int;
@@ -213,6 +229,14 @@ extern "C" {
     pub fn eccx_bls_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8,
                                dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void, d_verdicts: *mut c_void, opts: u32,
                                stream: *mut c_void) -> c_int;
+    // AggregateVerify: one aggregate signature against the (key, message) pairs group_offsets[i] .. group_offsets[i + 1]
+    pub fn eccx_bls_aggregate_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8,
+                                     dst_len: usize, sigs: *const u8, pubkeys: *const u8, group_offsets: *const u64, terms: usize,
+                                     verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_bls_aggregate_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void,
+                                         dst: *const u8, dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void,
+                                         d_group_offsets: *const c_void, terms: usize, d_verdicts: *mut c_void, opts: u32,
+                                         stream: *mut c_void) -> c_int;
     pub fn eccx_bls_fast_aggregate_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8,
                                           dst_len: usize, sigs: *const u8, pubkeys: *const u8, key_offsets: *const u64, keys: usize,
                                           verdicts: *mut u8, opts: u32) -> c_int;

@@ -34,6 +34,7 @@ pub use weierstrass::{p256r1, p384r1, p521r1};
 // one).  Invoked here: weierstrass.rs lists the three NIST curves, and tests/test_rust_ffi.py maps exactly those.
 gpu_weierstrass_curve!(p256k1, eccoxide::curve::sec2::p256k1, crate::ffi::ECCX_P256K1, 32, 32);
 pub mod bls;
+pub mod bls_aggregate;
 pub mod bls12_381_g1;
 pub mod ecdsa;
 pub mod ed25519;
