@@ -88,6 +88,12 @@ SYMBOLS = {
     "eccx_bls_aggregate_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, c_uint32]),
     "eccx_bls_aggregate_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p,
                                               c_size_t, c_void_p, c_uint32, c_void_p]),
+    "eccx_scalarmul_u64": (c_int, [c_void_p, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_scalarmul_u64_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_bls_batch_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p, c_size_t, _u8p, _u8p, _u8p,
+                                      c_uint32]),
+    "eccx_bls_batch_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_comb_table": (c_int, [c_void_p, c_int, _u8p]),
     "eccx_scalarmul_var_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_scalarmul_base_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, c_uint32]),

@@ -57,8 +57,9 @@ const CurveOps* ops_of(int curve) {
 //   B_MSM      the workspace of eccx_msm_dev (kernels_msm.hpp lays it out)
 //   B_BLS      the working slab of the eccx_bls_* entry points (BlsSlab below)
 //   B_BLSAGG   the working slab of eccx_bls_aggregate_verify (BlsAggSlab below)
+//   B_BLSBATCH the working slab of eccx_bls_batch_verify (BlsBatchSlab below)
 enum { IO_K = 0, IO_P = 1, IO_O = 2, IO_F = 3, IO_J = 4, IO_A = 5, IO_B = 6, NIO = 7 };
-enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, NBUF };
+enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, B_BLSBATCH, NBUF };
 struct DevBuf {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -325,6 +326,52 @@ int ensure_bls_agg_slab(eccx_ctx* ctx, size_t n, size_t terms, BlsAggSlab* out) 
   if (rc || !out) return rc;
   Carve c{base};
   *out = BlsAggSlab::lay(c, n, terms);
+  return ECCX_OK;
+}
+// Batch verification, n members in `batches` batches, records at the wider group's size as above: the decoded keys,
+// signatures and H(m) of the members (n x 192 each) with their flags, scaled in place; the sums of the pieces the scaled
+// signatures are cut into (n / 64 + batches + 1 of them and an empty group in front, x 192) with their flags, the pieces'
+// member offsets and the batches' piece offsets; the batches' sums (batches x 192) with theirs; the flat terms of the ragged pairing product (n + batches: g1 x 96, g2 x 192, a
+// flag byte each per side) with their batches + 1 offsets; what the members' flags decide per batch (batches words); the
+// pairing's verdicts (batches).  Every piece grows with n and with batches.
+struct BlsBatchSlab {
+  uint8_t *key, *key_fl, *sig, *sig_fl, *h, *h_fl, *piece, *piece_fl, *poff, *boff, *agg, *agg_fl, *g1, *g2, *g1_inf, *g2_inf, *toff, *pre, *pv;
+  static BlsBatchSlab lay(Carve& c, size_t n, size_t batches) {
+    const size_t flat = n + batches, pieces = eccx::bls_batch_pieces(n, batches);
+    return {c.take(n * 192), c.take(n), c.take(n * 192), c.take(n), c.take(n * 192), c.take(n), c.take((pieces + 1) * 192), c.take(pieces + 1),
+            c.take((pieces + 2) * sizeof(uint64_t)), c.take((batches + 1) * sizeof(uint64_t)), c.take(batches * 192), c.take(batches),
+            c.take(flat * 96), c.take(flat * 192), c.take(flat), c.take(flat), c.take((batches + 1) * sizeof(uint64_t)),
+            c.take(batches * sizeof(uint32_t)), c.take(batches)};
+  }
+};
+// out == nullptr: only size the slab (eccx_reserve)
+int ensure_bls_batch_slab(eccx_ctx* ctx, size_t n, size_t batches, BlsBatchSlab* out) {
+  Carve size{nullptr};
+  BlsBatchSlab::lay(size, n, batches);
+  uint8_t* base = nullptr;
+  const int rc = grow(ctx, B_BLSBATCH, size.end, &base);
+  if (rc || !out) return rc;
+  Carve c{base};
+  *out = BlsBatchSlab::lay(c, n, batches);
+  return ECCX_OK;
+}
+// The device copies of eccx_bls_batch_verify's host form beside the messages' (EdMsgs: IO_J the bytes, IO_K the n + 1
+// offsets): IO_A the batch offsets, IO_B the keys, IO_P the signatures with the coefficients behind them, IO_O the member
+// statuses, IO_F the verdicts.  out == nullptr: only size the slots (eccx_reserve).
+struct BlsBatchIo {
+  uint8_t *bo, *keys, *sigs, *coeffs, *status, *verdicts;
+};
+int bls_batch_host_slots(eccx_ctx* ctx, size_t n, size_t batches, size_t key_enc, size_t sig_enc, BlsBatchIo* out) {
+  BlsBatchIo io = {};
+  int rc = grow(ctx, B_IO + IO_K, (n + 1) * sizeof(uint64_t));
+  if (!rc) rc = grow(ctx, B_IO + IO_A, (batches + 1) * sizeof(uint64_t), &io.bo);
+  if (!rc) rc = grow(ctx, B_IO + IO_B, n * key_enc + 1, &io.keys);
+  if (!rc) rc = grow(ctx, B_IO + IO_P, align16(n * sig_enc) + n * 8 + 1, &io.sigs);
+  if (!rc) rc = grow(ctx, B_IO + IO_O, n + 1, &io.status);
+  if (!rc) rc = grow(ctx, B_IO + IO_F, batches + 1, &io.verdicts);
+  if (rc) return rc;
+  io.coeffs = io.sigs + align16(n * sig_enc);
+  if (out) *out = io;
   return ECCX_OK;
 }
 // out == nullptr: only size the slab (eccx_reserve)
@@ -1022,6 +1069,17 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     if (!rc) rc = ensure_rows(ctx, g2, 2 * max_n);
     if (!rc) rc = ensure_rows(ctx, g1, max_n);
     if (!rc) rc = ensure_pairing_groups(ctx, need_pairing_groups(ctx, g2, max_n, max_n));
+  }
+  // eccx_bls_batch_verify, n + batches <= max_n: its slab, the hash's rows on either curve (two per message on G2; the
+  // short multiplications and the batches' sums take one row per member or batch) and the ragged product over n + batches
+  // flat terms; with ECCX_PREP_HOST the host form's copies (bls_batch_host_slots; message bytes apart, which no n bounds)
+  if (!rc && (what & ECCX_PREP_BLS_BATCH)) {
+    rc = ensure_bls_batch_slab(ctx, max_n, max_n, nullptr);
+    const CurveOps *g1 = ops_of(ECCX_BLS12_381_G1), *g2 = ops_of(ECCX_BLS12_381_G2);
+    if (!rc) rc = ensure_rows(ctx, g2, 2 * max_n);
+    if (!rc) rc = ensure_rows(ctx, g1, max_n);
+    if (!rc) rc = ensure_pairing_groups(ctx, need_pairing_groups(ctx, g2, max_n, max_n));
+    if (!rc && (what & ECCX_PREP_HOST)) rc = bls_batch_host_slots(ctx, max_n, max_n, 96, 96, nullptr);
   }
   // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
   // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
@@ -2202,6 +2260,158 @@ int eccx_bls_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, cons
     return rc;
   }
   HIP_TRY(ctx, settled(hipMemcpyAsync(verdicts, d_v, n, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
+}
+
+namespace {
+// eccx_scalarmul_u64[_dev]: everything checkable before a device is touched
+int scalarmul_u64_args(eccx_ctx* ctx, int curve, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (curve != ECCX_BLS12_381_G1 && curve != ECCX_BLS12_381_G2)
+    return arg_err(ctx, "eccx_scalarmul_u64: ECCX_BLS12_381_G1 and ECCX_BLS12_381_G2 only");
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS)
+    return arg_err(ctx, "eccx_scalarmul_u64: opts must be 0 or ECCX_VALIDATE_POINTS (coefficients are public: there is no ECCX_CT_SCAN form)");
+  return ECCX_OK;
+}
+const char* const BLS_BATCH_OPTS = "eccx_bls_batch_verify: opts must be 0 or ECCX_BLS_MIN_SIG";
+int bls_batch_sizes(eccx_ctx* ctx, size_t n, size_t batches) {
+  if (n > PAIRING_GROUPS_MAX / 2 || batches > PAIRING_GROUPS_MAX / 2 - n) return arg_err(ctx, "eccx_bls_batch_verify: n + batches above 2^30");
+  return ECCX_OK;
+}
+}  // namespace
+
+int eccx_scalarmul_u64_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_coeffs, const void* d_points, const void* d_inf, void* d_out,
+                           void* d_out_inf, uint32_t opts, void* stream) {
+  if (int rc = scalarmul_u64_args(ctx, curve, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_coeffs && d_points && d_out && d_out_inf)) return rc;
+  const CurveOps* ops = ops_of(curve);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t* flags = static_cast<uint8_t*>(d_out_inf);
+  // one homogeneous row per unit (the kernel parks 2P in it on the way), then the group law's normalisation
+  if (int rc = ensure_rows(ctx, ops, n)) return rc;
+  HIP_TRY(ctx, eccx::launch_scalarmul_u64(s, ctx->cus, curve == ECCX_BLS12_381_G2, n, static_cast<const uint8_t*>(d_coeffs),
+                                          static_cast<const uint8_t*>(d_points), static_cast<const uint8_t*>(d_inf), ctx->rows(), flags,
+                                          kopts_of(opts)));
+  HIP_TRY(ctx, ops->to_affine_add_u(norm_grid(ctx, n), s, n, ctx->rows(), static_cast<uint8_t*>(d_out), flags));
+  return ECCX_OK;
+}
+
+int eccx_scalarmul_u64(eccx_ctx* ctx, int curve, size_t n, const uint8_t* coeffs, const uint8_t* points, const uint8_t* inf, uint8_t* out,
+                       uint8_t* out_inf, uint32_t opts) {
+  if (int rc = scalarmul_u64_args(ctx, curve, opts)) return rc;
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, coeffs && points && out && out_inf)) return rc;
+  const size_t pb = 2 * (size_t)ops_of(curve)->info.fb;
+  HostBuf bufs[] = {in_buf(IO_K, coeffs, 8), in_buf(IO_P, points, pb), in_buf(IO_A, inf, 1), out_buf(IO_O, out, pb), out_buf(IO_F, out_inf, 1)};
+  return host_pipeline(ctx, n, bufs, /*chunked=*/true, [&](size_t, size_t cnt, uint8_t* const* d) {
+    return eccx_scalarmul_u64_dev(ctx, curve, cnt, d[0], d[1], d[2], d[3], d[4], opts, ctx->stream);
+  });
+}
+
+// eccx_bls_batch_verify_dev: the decoders, the hash, the members' flags, the two short multiplications, the sums by batch, the
+// ragged assembly, the ragged product, the fold, on one stream
+int eccx_bls_batch_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                              const void* d_sigs, const void* d_pubkeys, const void* d_coeffs, size_t batches,
+                              const void* d_batch_offsets, void* d_verdicts, void* d_member_status, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_BATCH_OPTS)) return rc;
+  if (n == 0 && batches == 0) return ECCX_OK;
+  if (int rc = bls_batch_sizes(ctx, n, batches)) return rc;
+  if (int rc = begin_batch(ctx, (dst || dst_len == 0) && (batches == 0 || (d_batch_offsets && d_verdicts)) &&
+                                    (n == 0 || (d_msgs && d_offsets && d_sigs && d_pubkeys && d_coeffs))))
+    return rc;
+  const BlsWhat& w = *bls_what(opts);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BlsBatchSlab b;
+  if (int rc = ensure_bls_batch_slab(ctx, n, batches, &b)) return rc;
+  uint8_t* verdicts = static_cast<uint8_t*>(d_verdicts);
+  const uint64_t* bo = static_cast<const uint64_t*>(d_batch_offsets);
+  const uint8_t* coeffs = static_cast<const uint8_t*>(d_coeffs);
+  uint32_t* pre = reinterpret_cast<uint32_t*>(b.pre);
+  if (batches) HIP_TRY(ctx, hipMemsetAsync(pre, 0, batches * sizeof(uint32_t), s));
+  // the G1 operand of a member's pair is what the coefficient scales: the key for min-pk, H(m) for min-sig
+  uint8_t *scaled = w.min_sig ? b.h : b.key, *scaled_fl = w.min_sig ? b.h_fl : b.key_fl;
+  uint8_t *other = w.min_sig ? b.key : b.h, *other_fl = w.min_sig ? b.key_fl : b.h_fl;
+  if (n) {
+    // every key through the decoder, its subgroup test and KeyValidate (the identity is no key); every signature through
+    // its decoder; every message through the hash, whose output lands in the slab before anything reuses the rows it worked in
+    if (int rc = eccx_point_decompress_dev(ctx, w.key_curve, n, d_pubkeys, b.key, b.key_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+    HIP_TRY(ctx, eccx::launch_bls_key_flags(s, n, b.key_fl));
+    if (int rc = eccx_point_decompress_dev(ctx, w.sig_curve, n, d_sigs, b.sig, b.sig_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+    if (int rc = hash_to_curve_dev(ctx, *w.h2c, n, d_msgs, d_offsets, dst, dst_len, b.h, b.h_fl, 0, s)) return rc;
+    // the statuses come from the flags as the decoders left them; the scaling below keeps every 2 and adds only 1s
+    HIP_TRY(ctx, eccx::launch_bls_batch_flags(s, n, batches, bo, coeffs, b.key_fl, b.sig_fl, b.h_fl, pre,
+                                              static_cast<uint8_t*>(d_member_status)));
+    if (batches == 0) return ECCX_OK;
+    // c_i times the G1 operand and c_i sig_i, in place, each with the normalisation behind it
+    if (int rc = eccx_scalarmul_u64_dev(ctx, ECCX_BLS12_381_G1, n, coeffs, scaled, scaled_fl, scaled, scaled_fl, 0, s)) return rc;
+    if (int rc = eccx_scalarmul_u64_dev(ctx, w.sig_curve, n, coeffs, b.sig, b.sig_fl, b.sig, b.sig_fl, 0, s)) return rc;
+  }
+  // one sum of scaled signatures per batch, in two levels of eccx_point_sum's kernels: each batch's members cut at the
+  // multiples of 64 (group 0 of the first level is empty, group q + 1 is piece q), then each batch's pieces.  A range that
+  // decreases or leaves n writes no piece, ends flagged 2 and reads nothing.
+  if (n) {
+    const size_t pieces = eccx::bls_batch_pieces(n, batches), pb = w.sig_pb;
+    HIP_TRY(ctx, eccx::launch_bls_batch_pieces(s, n, batches, bo, reinterpret_cast<uint64_t*>(b.poff), reinterpret_cast<uint64_t*>(b.boff)));
+    if (int rc = eccx_point_sum_dev(ctx, w.sig_curve, pieces + 1, b.poff, n, b.sig, b.sig_fl, b.piece, b.piece_fl, 0, s)) return rc;
+    if (int rc = eccx_point_sum_dev(ctx, w.sig_curve, batches, b.boff, pieces, b.piece + pb, b.piece_fl + 1, b.agg, b.agg_fl, 0, s)) return rc;
+  } else {
+    if (int rc = eccx_point_sum_dev(ctx, w.sig_curve, batches, bo, 0, b.sig, b.sig_fl, b.agg, b.agg_fl, 0, s)) return rc;
+  }
+  HIP_TRY(ctx, eccx::launch_bls_batch_assemble(s, n, batches, w.min_sig, bo, scaled, scaled_fl, other, other_fl, b.agg, b.agg_fl, pre, b.g1,
+                                               b.g1_inf, b.g2, b.g2_inf, reinterpret_cast<uint64_t*>(b.toff), verdicts));
+  if (int rc = pairing_groups_dev(ctx, batches, n + batches, b.g1, b.g1_inf, b.g2, b.g2_inf, b.toff, nullptr, false, b.pv, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_bls_fold(s, batches, b.pv, verdicts));
+  return ECCX_OK;
+}
+
+int eccx_bls_batch_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                          const uint8_t* sigs, const uint8_t* pubkeys, const uint8_t* coeffs, size_t batches,
+                          const uint64_t* batch_offsets, uint8_t* verdicts, uint8_t* member_status, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (int rc = bls_opts(ctx, opts, false, BLS_BATCH_OPTS)) return rc;
+  if (n == 0 && batches == 0) return ECCX_OK;
+  if (int rc = bls_batch_sizes(ctx, n, batches)) return rc;
+  if ((!dst && dst_len != 0) || (batches && (!batch_offsets || !verdicts)) || (n && (!offsets || !sigs || !pubkeys || !coeffs)))
+    return arg_err(ctx, "null buffer");
+  for (size_t i = 0; i < batches; ++i)
+    if (batch_offsets[i + 1] < batch_offsets[i]) return arg_err(ctx, "eccx_bls_batch_verify: the batch offsets decrease");
+  if (batches && batch_offsets[batches] - batch_offsets[0] > n)
+    return arg_err(ctx, "eccx_bls_batch_verify: the last batch offset lies beyond the members");
+  EdMsgs m{msgs, offsets};
+  if (n) {
+    if (int rc = m.check(ctx, n, "eccx_bls_batch_verify: the offsets decrease")) return rc;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n) {
+    if (int rc = m.grow_slots(ctx, n)) return rc;
+  }
+  const BlsWhat& w = *bls_what(opts);
+  BlsBatchIo io;
+  if (int rc = bls_batch_host_slots(ctx, n, batches, w.key_enc, w.sig_enc, &io)) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  if (batches) HIP_TRY(ctx, settled(hipMemcpyAsync(io.bo, batch_offsets, (batches + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s)));
+  if (n) {
+    HIP_TRY(ctx, settled(hipMemcpyAsync(io.sigs, sigs, n * w.sig_enc, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(hipMemcpyAsync(io.keys, pubkeys, n * w.key_enc, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(hipMemcpyAsync(io.coeffs, coeffs, n * 8, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(m.copy_in(0, n, s)));
+  }
+  const int rc = eccx_bls_batch_verify_dev(ctx, n, n ? m.dev_msgs(0) : nullptr, n ? m.dev_offsets(0) : nullptr, dst, dst_len, io.sigs, io.keys,
+                                           io.coeffs, batches, io.bo, io.verdicts, member_status ? io.status : nullptr, opts, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  if (batches) HIP_TRY(ctx, settled(hipMemcpyAsync(verdicts, io.verdicts, batches, hipMemcpyDeviceToHost, s)));
+  if (n && member_status) HIP_TRY(ctx, settled(hipMemcpyAsync(member_status, io.status, n, hipMemcpyDeviceToHost, s)));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return ECCX_OK;
 }

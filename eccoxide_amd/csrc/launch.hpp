@@ -280,6 +280,29 @@ hipError_t launch_bls_assemble_groups(hipStream_t s, size_t n, size_t terms, int
                                       const uint64_t* group_offsets, const uint32_t* pre, uint8_t* g1, uint8_t* g1_inf, uint8_t* g2,
                                       uint8_t* g2_inf, uint64_t* term_offsets, uint8_t* verdicts);
 
+// the short public-scalar multiplication [c]P, c 8 big-endian bytes, on bls12_381_g1 (g2 == 0) and bls12_381_g2 (kernels_bls_batch.hpp,
+// k_bls12_381_batch.hip): leaves n homogeneous rows for to_affine_add_u and 0 / 2 in flags, which may be the buffer `inf`
+// points at (1: the operand is the identity; 2: rejected).  Picks its own grid; opts: OPT_VALIDATE.
+hipError_t launch_scalarmul_u64(hipStream_t s, int cus, int g2, size_t n, const uint8_t* coeffs, const uint8_t* points, const uint8_t* inf,
+                                uint32_t* rows, uint8_t* flags, uint32_t opts);
+// Batch verification: batch b holds members batch_offsets[b] .. batch_offsets[b + 1] of n.  launch_bls_batch_flags writes the
+// members' statuses (member_status may be null) and ORs what each decides into its batch's word of `pre` (zeroed by the caller
+// on the stream: bit 0 malformed, bit 1 a key that fails KeyValidate); launch_bls_batch_assemble writes batch b's L_b + 1 terms
+// at flat positions batch_offsets[b] - batch_offsets[0] + b + j, the last being the sum of the scaled signatures against the
+// negated generator, the batches + 1 term offsets of the ragged pairing product, and the verdicts the flags already decide.
+hipError_t launch_bls_batch_flags(hipStream_t s, size_t n, size_t batches, const uint64_t* batch_offsets, const uint8_t* coeffs,
+                                  const uint8_t* key_fl, const uint8_t* sig_fl, const uint8_t* h_fl, uint32_t* pre, uint8_t* member_status);
+// the two levels of a batch's signature sum: bls_batch_pieces(n, batches) piece ids, a batch's pieces being its members cut at
+// the multiples of 64.  launch_bls_batch_pieces fills `slots` (pieces + 2 values: the member offsets of pieces + 1 groups for
+// the point sum, group 0 being empty and group q + 1 piece q) and the batches + 1 piece offsets of the batches.
+size_t bls_batch_pieces(size_t n, size_t batches);
+hipError_t launch_bls_batch_pieces(hipStream_t s, size_t n, size_t batches, const uint64_t* batch_offsets, uint64_t* slots,
+                                   uint64_t* batch_pieces);
+hipError_t launch_bls_batch_assemble(hipStream_t s, size_t n, size_t batches, int min_sig, const uint64_t* batch_offsets,
+                                     const uint8_t* scaled, const uint8_t* scaled_fl, const uint8_t* other, const uint8_t* other_fl,
+                                     const uint8_t* agg, const uint8_t* agg_fl, const uint32_t* pre, uint8_t* g1, uint8_t* g1_inf,
+                                     uint8_t* g2, uint8_t* g2_inf, uint64_t* term_offsets, uint8_t* verdicts);
+
 constexpr int LAUNCH_WG = 256;
 
 template <class K>

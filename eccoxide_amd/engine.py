@@ -46,6 +46,7 @@ PREP_MSM = 16384
 PREP_BLS = 32768
 PREP_PAIRING_GROUPS = 65536
 PREP_BLS_AGGREGATE = 131072
+PREP_BLS_BATCH = 262144
 PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
@@ -172,7 +173,7 @@ class Engine:
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
                 h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False, bls: bool = False,
-                pairing_groups: bool = False, bls_aggregate: bool = False):
+                pairing_groups: bool = False, bls_aggregate: bool = False, bls_batch: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
@@ -184,7 +185,8 @@ class Engine:
         (curve "bls12_381_g2") and what their parts need on both curves, for max(n, keys) <= max_n; pairing_groups: the
         slab and rows of pairing_groups / pairing_check_groups (curve "bls12_381_g2") for every shape with n + terms <=
         max_n; bls_aggregate: the slab of bls_aggregate_verify (curve "bls12_381_g2") and what its parts need, for n + terms
-        <= max_n."""
+        <= max_n; bls_batch: the slab of bls_batch_verify (curve "bls12_381_g2") and what its parts need, for n + batches <=
+        max_n (with host: the host form's copies, message bytes apart)."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
@@ -194,7 +196,8 @@ class Engine:
                                            | (PREP_PAIRING if pairing else 0) | (PREP_X448 if x448 else 0)
                                            | (PREP_MSM if msm else 0) | (PREP_BLS if bls else 0)
                                            | (PREP_PAIRING_GROUPS if pairing_groups else 0)
-                                           | (PREP_BLS_AGGREGATE if bls_aggregate else 0)))
+                                           | (PREP_BLS_AGGREGATE if bls_aggregate else 0)
+                                           | (PREP_BLS_BATCH if bls_batch else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -561,6 +564,115 @@ class Engine:
                                                             group_offsets.data_ptr(), terms, verdicts.data_ptr(),
                                                             BLS_MIN_SIG if min_sig else 0, stream))
         return verdicts
+
+    def scalarmul_u64(self, curve, coeffs: bytes, points: bytes, inf: Optional[bytes] = None, *, validate: bool = False):
+        """out[i] = coeffs[i] * points[i] for 64-bit PUBLIC coefficients (n x 8 bytes, big-endian) on bls12_381_g1 or
+        bls12_381_g2 (eccx_scalarmul_u64); inf: None or n flag bytes (1: the operand is the identity, 2: rejected).
+        Returns (affine bytes, flags).  There is no secret-scalar form: never pass a secret here."""
+        cid = curve_id(curve)
+        if len(coeffs) % 8:
+            raise ValueError("coeffs length is not a multiple of 8")
+        n = len(coeffs) // 8
+        pb = 2 * field_bytes(cid) if cid in (BLS12_381_G1, BLS12_381_G2) else 0
+        if pb and (len(points) != n * pb or (inf is not None and len(inf) != n)):
+            raise ValueError(f"points must hold n x {pb} bytes and inf n bytes")
+        out = ctypes.create_string_buffer(max(1, n * pb))
+        flags = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_scalarmul_u64(self._ctx, cid, n, coeffs, points, inf, out, flags, VALIDATE_POINTS if validate else 0))
+        return out.raw[:n * pb], flags.raw[:n]
+
+    def scalarmul_u64_t(self, curve, coeffs, points, inf=None, out=None, flags=None, *, validate: bool = False,
+                        stream: Optional[int] = None):
+        """Device-tensor form of scalarmul_u64 (eccx_scalarmul_u64_dev); enqueued on the stream, nothing is synchronised.
+        out may be points and flags may be inf: the call then works in place."""
+        import torch
+
+        cid = curve_id(curve)
+        if cid not in (BLS12_381_G1, BLS12_381_G2):
+            raise ValueError("scalarmul_u64: bls12_381_g1 and bls12_381_g2 only")
+        n, pb = self._units(coeffs, 8, "coeffs"), 2 * field_bytes(cid)
+        out = torch.empty((n, pb), dtype=torch.uint8, device=coeffs.device) if out is None else out
+        flags = torch.empty((n,), dtype=torch.uint8, device=coeffs.device) if flags is None else flags
+        self._tensors(n, ("coeffs", coeffs, 8), ("points", points, pb), ("inf", inf, 1), ("out", out, pb), ("flags", flags, 1))
+        stream = torch.cuda.current_stream(coeffs.device).cuda_stream if stream is None else stream
+        self._check(self._lib.eccx_scalarmul_u64_dev(self._ctx, cid, n, coeffs.data_ptr(), points.data_ptr(),
+                                                     None if inf is None else inf.data_ptr(), out.data_ptr(), flags.data_ptr(),
+                                                     VALIDATE_POINTS if validate else 0, stream))
+        return out, flags
+
+    @staticmethod
+    def draw_batch_coeffs(n: int) -> bytes:
+        """n nonzero 64-bit coefficients from the operating system's generator (the `secrets` module), 8 bytes each."""
+        import secrets
+
+        out = bytearray()
+        for _ in range(n):
+            c = secrets.token_bytes(8)
+            while not any(c):  # a zero coefficient would drop its signature out of the check (the C ABI answers MALFORMED)
+                c = secrets.token_bytes(8)
+            out += c
+        return bytes(out)
+
+    def bls_batch_verify(self, messages, sigs: bytes, pubkeys: bytes, dst: bytes, *, batches=None, coeffs: Optional[bytes] = None,
+                         min_sig: bool = False):
+        """Batch verification by a random linear combination (eccx_bls_batch_verify): one verdict per BATCH of (message,
+        signature, key) triples, e(-G, sum c_i sig_i) prod e(c_i pk_i, H(m_i)) = 1, with one final exponentiation and L + 1
+        Miller terms per batch of L.  batches: the batch sizes, in order (None: one batch of everything); triples beyond
+        their sum belong to no batch.  Returns (verdicts, member_status): MALFORMED before BAD_KEY before the equation; the
+        empty batch is VALID; member_status is MALFORMED / BAD_KEY where that member alone decides its batch, else VALID,
+        which says nothing about the member's own equation.
+
+        coeffs: n x 8 bytes, big-endian, nonzero.  None draws them here, from the `secrets` module, redrawing a zero.  THIS
+        IS THE ONLY PLACE RANDOMNESS IS DRAWN: the C ABI is a deterministic function of its inputs, and the check is sound
+        only if whoever produced the signatures could not predict the coefficients (a bad batch then passes with
+        probability at most 2^-64).  Fixed or guessable coefficients are no check at all -- with all ones, the forgery
+        (sig_1 + D, sig_2 - D) verifies -- so pass coeffs only to reproduce a computation, never in production."""
+        import numpy as np
+
+        n = len(messages)
+        kb, sb = self._bls_sizes(min_sig)
+        sizes = [n] if batches is None else [int(b) for b in batches]
+        if any(b < 0 for b in sizes) or sum(sizes) > n:
+            raise ValueError("batch sizes must not be negative and must not exceed the triples")
+        coeffs = self.draw_batch_coeffs(n) if coeffs is None else bytes(coeffs)
+        if len(sigs) != n * sb or len(pubkeys) != n * kb or len(coeffs) != n * 8:
+            raise ValueError(f"one signature of {sb} bytes, one key of {kb} bytes and one coefficient of 8 bytes per message")
+        nb = len(sizes)
+        batch_offsets = np.zeros(nb + 1, dtype=np.uint64)
+        np.cumsum(sizes, out=batch_offsets[1:])
+        msgs, offsets = self._ragged(messages)
+        dst = bytes(dst)
+        verdicts = ctypes.create_string_buffer(max(1, nb))
+        status = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_bls_batch_verify(self._ctx, n, msgs if msgs else None, offsets.ctypes.data, dst if dst else None,
+                                                    len(dst), sigs, pubkeys, coeffs, nb, batch_offsets.ctypes.data, verdicts, status,
+                                                    BLS_MIN_SIG if min_sig else 0))
+        return verdicts.raw[:nb], status.raw[:n]
+
+    def bls_batch_verify_t(self, msgs, offsets, sigs, pubkeys, coeffs, batch_offsets, dst: bytes, verdicts=None, member_status=None, *,
+                           min_sig: bool = False, stream: Optional[int] = None):
+        """Device-tensor form of bls_batch_verify (eccx_bls_batch_verify_dev): coeffs n x 8 bytes (the caller draws them: see
+        bls_batch_verify), batch_offsets a contiguous int64 CUDA tensor of batches + 1 entries into the n triples.  A range
+        that decreases or leaves the triples makes its batch SIG_MALFORMED alone.  Returns (verdicts, member_status)."""
+        import torch
+
+        n, msgs = self._bls_msgs_t(msgs, offsets)
+        kb, sb = self._bls_sizes(min_sig)
+        if batch_offsets.dtype not in (torch.int64, torch.uint64) or batch_offsets.numel() < 1 or not batch_offsets.is_contiguous() \
+                or not batch_offsets.is_cuda or batch_offsets.device.index != self.device:
+            raise ValueError("batch_offsets must be a contiguous int64 CUDA tensor of batches + 1 entries on this engine's GPU")
+        nb = batch_offsets.numel() - 1
+        verdicts = torch.empty((nb,), dtype=torch.uint8, device=offsets.device) if verdicts is None else verdicts
+        member_status = torch.empty((n,), dtype=torch.uint8, device=offsets.device) if member_status is None else member_status
+        self._tensors(nb, ("verdicts", verdicts, 1))
+        stream = self._bls_t(n, (("sigs", sigs, sb), ("pubkeys", pubkeys, kb), ("coeffs", coeffs, 8), ("member_status", member_status, 1)),
+                             stream, offsets)
+        dst = bytes(dst)
+        self._check(self._lib.eccx_bls_batch_verify_dev(self._ctx, n, msgs.data_ptr(), offsets.data_ptr(), dst if dst else None, len(dst),
+                                                        sigs.data_ptr(), pubkeys.data_ptr(), coeffs.data_ptr(), nb,
+                                                        batch_offsets.data_ptr(), verdicts.data_ptr(), member_status.data_ptr(),
+                                                        BLS_MIN_SIG if min_sig else 0, stream))
+        return verdicts, member_status
 
     def msm_window_bits(self, n: int) -> int:
         """The window width msm uses for n terms (a pure function of n)."""

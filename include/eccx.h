@@ -289,6 +289,11 @@ enum {
   ECCX_PREP_BLS_AGGREGATE = 1u << 17, /* eccx_reserve (bls12_381_g2): the working slab of eccx_bls_aggregate_verify for n +
                                    terms <= max_n (a slab of its own: ECCX_PREP_BLS reserves what it did before), and with it
                                    what the decoders, the hash and the ragged pairing product need */
+  ECCX_PREP_BLS_BATCH = 1u << 18, /* eccx_reserve (bls12_381_g2): the working slab of eccx_bls_batch_verify for n + batches <=
+                                   max_n (a slab of its own: ECCX_PREP_BLS and ECCX_PREP_BLS_AGGREGATE reserve what they did
+                                   before), and with it what the decoders, the hash, the short multiplications, the sums and
+                                   the ragged pairing product need; with ECCX_PREP_HOST the host form's copies of everything
+                                   but the message bytes, which no n bounds */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -689,6 +694,29 @@ int eccx_point_sum(eccx_ctx* ctx, int curve, size_t n, const uint64_t* offsets, 
 int eccx_point_sum_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_offsets, size_t members, const void* d_points,
                        const void* d_inf, void* d_out, void* d_flags, uint32_t opts, void* stream);
 
+/* Multiplication by a short PUBLIC scalar: out[i] = [c_i] P_i, c_i a 64-bit coefficient -- the scaling step of batch
+ * verification by a random linear combination (eccx_bls_batch_verify), where the 255-bit ladder of eccx_scalarmul_var with
+ * a zero-padded scalar would do four times the doublings.  One lane per unit: signed 2-bit windows over {P, 2P}, 65
+ * doublings and 33 complete additions, no table memory.
+ * THE COEFFICIENTS ARE PUBLIC: the kernel's selects follow their digits and there is no ECCX_CT_SCAN form.  Never pass a
+ * secret here.
+ *   curve   : ECCX_BLS12_381_G1 or ECCX_BLS12_381_G2; any other id is ECCX_ERR_ARG
+ *   coeffs  : n x 8 bytes, big-endian
+ *   points  : n affine x || y records of 96 (G1) or 192 (G2) bytes, as eccx_scalarmul_var takes them.  Any point of the
+ *             curve is legal, in the prime-order subgroup or not.
+ *   inf     : NULL or n flag bytes: 1 -- the operand is the identity, whatever its coordinate bytes are; 2 -- rejected
+ *   out     : n records; out_inf: n bytes -- 0 a point, ECCX_FLAG_INFINITY the result is the identity (zero bytes: the
+ *             coefficient 0, an identity operand, or a coefficient that is a multiple of the point's order),
+ *             ECCX_FLAG_REJECTED (zero bytes).  out may be points and out_inf may be inf: the call then works in place.
+ *   opts    : 0 or ECCX_VALIDATE_POINTS (an operand not flagged 1 with a coordinate >= p or off the curve is rejected).
+ *             ECCX_CT_SCAN and every other bit are ECCX_ERR_ARG, returned before anything is launched or written.
+ * n == 0 returns ECCX_OK.  The _dev form enqueues on `stream` and returns; it works in the context's row buffer, so after
+ * eccx_reserve(ctx, curve, max_n, 0) a call with n <= max_n neither allocates, frees nor synchronises. */
+int eccx_scalarmul_u64(eccx_ctx* ctx, int curve, size_t n, const uint8_t* coeffs, const uint8_t* points, const uint8_t* inf,
+                       uint8_t* out, uint8_t* out_inf, uint32_t opts);
+int eccx_scalarmul_u64_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_coeffs, const void* d_points, const void* d_inf,
+                           void* d_out, void* d_out_inf, uint32_t opts, void* stream);
+
 /* BLS signatures on BLS12-381 (draft-irtf-cfrg-bls-signature): keys, signatures, verification and FastAggregateVerify, wire
  * bytes in, status or verdict bytes out, every step on the device on one stream.
  * Variant: min-pk by default (Ethereum's): public keys 48-byte zcash-compressed G1, signatures 96-byte compressed G2, H(m) =
@@ -771,6 +799,47 @@ int eccx_bls_aggregate_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, cons
 int eccx_bls_aggregate_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst,
                                   size_t dst_len, const void* d_sigs, const void* d_pubkeys, const void* d_group_offsets,
                                   size_t terms, void* d_verdicts, uint32_t opts, void* stream);
+
+/* Batch verification by a random linear combination: L (key, message, signature) triples with ONE final exponentiation and
+ * L + 1 Miller terms instead of L and 2 L,
+ *   min-pk:  e(-G1, sum c_i sig_i) * prod e(c_i pk_i, H(m_i)) = 1      min-sig:  e(sum c_i sig_i, -G2) * prod e(c_i H(m_i), pk_i) = 1
+ * with 64-bit coefficients c_i != 0 (coeffs: n x 8 bytes, big-endian).  Messages, tag, variants and encodings are exactly
+ * eccx_bls_verify's.  Batch b holds the members batch_offsets[b] .. batch_offsets[b + 1] (relative to batch_offsets[0]) of the
+ * n members; members beyond the last offset belong to no batch.  On the one stream: the key decoder with its subgroup test
+ * and KeyValidate, the signature decoder with its subgroup test, the hash, the members' statuses, eccx_scalarmul_u64's kernel
+ * on the G1 operand of each pair (the key for min-pk, H(m) for min-sig) and on the signatures, eccx_point_sum's kernels over
+ * the scaled signatures by batch, an assembly kernel that writes batch b's L_b + 1 terms at flat positions batch_offsets[b] +
+ * b + j (the last is the sum against the negated generator) with their term offsets, eccx_pairing_check_groups' kernels, and
+ * the fold onto ECCX_SIG_*.  verdicts: one byte per batch.
+ *   ECCX_SIG_MALFORMED  the batch's range decreases or leaves the n members (_dev form; such a batch reads nothing and the
+ *                       others stand); a member's signature does not decode or is outside the subgroup; a member's message
+ *                       offsets decrease; a member's coefficient is zero (its signature would drop out of the check)
+ *   ECCX_SIG_BAD_KEY    any member's key fails KeyValidate, the identity included
+ * MALFORMED before BAD_KEY; otherwise ECCX_SIG_VALID iff the equation holds with the caller's coefficients, else
+ * ECCX_SIG_INVALID.  The EMPTY batch is ECCX_SIG_VALID: there is nothing to refute and e(-G, O) = 1.  A decided batch's terms
+ * are flagged infinite: the pairing runs on nothing of it.
+ * member_status (NULL, or n bytes): ECCX_SIG_MALFORMED or ECCX_SIG_BAD_KEY where that member alone decides its batch, else
+ * ECCX_SIG_VALID, which means "nothing found by decoding" and says nothing about the member's equation.  Members outside
+ * every batch are decoded too and get their status.
+ * THE VERDICT IS A DETERMINISTIC FUNCTION OF THE INPUTS, COEFFICIENTS INCLUDED.  This library draws nothing (as with ECDSA
+ * nonces).  Soundness rests on the coefficients being unpredictable to whoever made the signatures: over uniformly drawn
+ * coefficients a batch with a bad member passes with probability at most 2^-64.  Predictable coefficients are no check: with
+ * all ones the equation is the plain sum check, which the forgery (sig_1 + D, sig_2 - D) passes.  Draw them from a
+ * cryptographic generator, per call, after the signatures are fixed.
+ * opts other than 0 or ECCX_BLS_MIN_SIG is ECCX_ERR_ARG; n + batches above 2^30 too.  n == 0 with batches > 0 is legal (every
+ * batch is empty); n == 0 and batches == 0 returns ECCX_OK.  The host form returns ECCX_ERR_ARG for null buffers, decreasing
+ * message or batch offsets and a last batch offset beyond n; the _dev form answers those per batch as above.  (Batches whose
+ * ranges overlap, possible only around a decreasing batch offset, share flat positions: their verdicts are then
+ * unspecified; an empty batch strictly inside another batch's range counts among them.  Where offsets decrease so far that
+ * a later batch lies BEFORE an earlier one, such batches may come back ECCX_SIG_MALFORMED: a batch's signatures are summed
+ * over exactly its range or the batch is refused, never over part of it.)  After eccx_reserve(ctx, ECCX_BLS12_381_G2, max_n, ECCX_PREP_BLS_BATCH) a _dev call with n + batches <= max_n
+ * neither allocates, frees nor synchronises. */
+int eccx_bls_batch_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                          const uint8_t* sigs, const uint8_t* pubkeys, const uint8_t* coeffs, size_t batches,
+                          const uint64_t* batch_offsets, uint8_t* verdicts, uint8_t* member_status, uint32_t opts);
+int eccx_bls_batch_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
+                              const void* d_sigs, const void* d_pubkeys, const void* d_coeffs, size_t batches,
+                              const void* d_batch_offsets, void* d_verdicts, void* d_member_status, uint32_t opts, void* stream);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

@@ -69,6 +69,7 @@ pub const ECCX_PREP_BLS: u32 = 1 << 15; // the working slab of the eccx_bls_* en
 pub const ECCX_PREP_MSM: u32 = 1 << 14; // eccx_msm's workspace for every n <= max_n (bls12_381_g1)
 pub const ECCX_PREP_PAIRING_GROUPS: u32 = 1 << 16; // eccx_pairing_groups' slab and rows for n + terms <= max_n (bls12_381_g2)
 pub const ECCX_PREP_BLS_AGGREGATE: u32 = 1 << 17; // eccx_bls_aggregate_verify's slab for n + terms <= max_n (bls12_381_g2)
+pub const ECCX_PREP_BLS_BATCH: u32 = 1 << 18; // eccx_bls_batch_verify's slab for n + batches <= max_n (bls12_381_g2)
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -216,6 +217,13 @@ extern "C" {
                               d_points: *const c_void, d_inf: *const c_void, d_out: *mut c_void, d_flags: *mut c_void, opts: u32,
                               stream: *mut c_void) -> c_int;
 
+    // [c]P for 64-bit PUBLIC coefficients (n x 8 bytes, big-endian) on BLS12-381 G1 or G2: the scaling step of batch verification
+    pub fn eccx_scalarmul_u64(ctx: *mut eccx_ctx, curve: c_int, n: usize, coeffs: *const u8, points: *const u8, inf: *const u8,
+                              out: *mut u8, out_inf: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_scalarmul_u64_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, d_coeffs: *const c_void, d_points: *const c_void,
+                                  d_inf: *const c_void, d_out: *mut c_void, d_out_inf: *mut c_void, opts: u32,
+                                  stream: *mut c_void) -> c_int;
+
     // BLS signatures: keys, signatures, verification, FastAggregateVerify (min-pk; ECCX_BLS_MIN_SIG swaps the groups)
     pub fn eccx_bls_public_key(ctx: *mut eccx_ctx, n: usize, secrets: *const u8, pubkeys: *mut u8, status: *mut u8, opts: u32) -> c_int;
     pub fn eccx_bls_public_key_dev(ctx: *mut eccx_ctx, n: usize, d_secrets: *const c_void, d_pubkeys: *mut c_void, d_status: *mut c_void,
@@ -237,6 +245,15 @@ extern "C" {
                                          dst: *const u8, dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void,
                                          d_group_offsets: *const c_void, terms: usize, d_verdicts: *mut c_void, opts: u32,
                                          stream: *mut c_void) -> c_int;
+    // batch verification by a random linear combination: one verdict per batch batch_offsets[b] .. batch_offsets[b + 1] of the n
+    // (message, signature, key) triples, with the caller's nonzero 64-bit coefficients
+    pub fn eccx_bls_batch_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8, dst_len: usize,
+                                 sigs: *const u8, pubkeys: *const u8, coeffs: *const u8, batches: usize, batch_offsets: *const u64,
+                                 verdicts: *mut u8, member_status: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_bls_batch_verify_dev(ctx: *mut eccx_ctx, n: usize, d_msgs: *const c_void, d_offsets: *const c_void, dst: *const u8,
+                                     dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void, d_coeffs: *const c_void,
+                                     batches: usize, d_batch_offsets: *const c_void, d_verdicts: *mut c_void,
+                                     d_member_status: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
     pub fn eccx_bls_fast_aggregate_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8,
                                           dst_len: usize, sigs: *const u8, pubkeys: *const u8, key_offsets: *const u64, keys: usize,
                                           verdicts: *mut u8, opts: u32) -> c_int;

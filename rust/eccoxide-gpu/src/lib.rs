@@ -35,6 +35,7 @@ pub use weierstrass::{p256r1, p384r1, p521r1};
 gpu_weierstrass_curve!(p256k1, eccoxide::curve::sec2::p256k1, crate::ffi::ECCX_P256K1, 32, 32);
 pub mod bls;
 pub mod bls_aggregate;
+pub mod bls_batch;
 pub mod bls12_381_g1;
 pub mod ecdsa;
 pub mod ed25519;
