@@ -74,6 +74,11 @@ SYMBOLS = {
     "eccx_msm": (c_int, [c_void_p, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_msm_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_msm_window_bits": (c_int, [c_size_t]),
+    "eccx_msm_batch": (c_int, [c_void_p, c_int, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_msm_batch_dev": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32,
+                                   c_void_p]),
+    "eccx_msm_batch_window_bits": (c_int, [c_size_t, c_size_t]),
+    "eccx_msm_batch_reserve": (c_int, [c_void_p, c_int, c_size_t, c_size_t]),
     "eccx_point_sum": (c_int, [c_void_p, c_int, c_size_t, _u8p, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_point_sum_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "eccx_bls_public_key": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, c_uint32]),

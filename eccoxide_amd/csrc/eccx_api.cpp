@@ -55,11 +55,13 @@ const CurveOps* ops_of(int curve) {
 //              and eccx_ecdsa_sign_dev / _public_key_dev (the *Slab layouts below), apart from the I/O slots, which the
 //              host-buffer forms fill with their copies
 //   B_MSM      the workspace of eccx_msm_dev (kernels_msm.hpp lays it out)
+//   B_MSMBATCH the workspace of eccx_msm_batch_dev (kernels_msm_batch.hpp lays it out), a slot of its own: B_MSM's sizing
+//              is eccx_msm's alone
 //   B_BLS      the working slab of the eccx_bls_* entry points (BlsSlab below)
 //   B_BLSAGG   the working slab of eccx_bls_aggregate_verify (BlsAggSlab below)
 //   B_BLSBATCH the working slab of eccx_bls_batch_verify (BlsBatchSlab below)
 enum { IO_K = 0, IO_P = 1, IO_O = 2, IO_F = 3, IO_J = 4, IO_A = 5, IO_B = 6, NIO = 7 };
-enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, B_BLSBATCH, NBUF };
+enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, B_BLSBATCH, B_MSMBATCH, NBUF };
 struct DevBuf {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -658,6 +660,30 @@ size_t msm_max_bytes(const CurveOps* ops, size_t n) {
   size_t bytes = 0;
   for (int lg = 0; lg <= floor_log2(n); ++lg)
     bytes = std::max(bytes, ops->msm_bytes(std::min(n, ((size_t)2 << lg) - 1), msm_bits_of_log2(lg)));
+  return bytes;
+}
+
+// eccx_msm_batch: the window width for m vectors of n terms, a function of (floor(log2 n), floor(log2 m)).  One vector is
+// eccx_msm's case and takes its width.  With more, m x W windows fill the machine and the addition count W x (n + 2^c)
+// decides: MSM_BATCH_WIDTH below is the fastest width the sweep of tools/bench_msm_batch.py measured (DESIGN.md section
+// 3.7o), never below eccx_msm's own.
+int msm_batch_bits_of_log2(int lg, int lgm) {
+  const int one = msm_bits_of_log2(lg);
+  if (lgm == 0) return one;
+  return std::min(16, std::max(one, std::max(4, lg - 3)));
+}
+int msm_batch_window_bits(size_t n, size_t m) { return msm_batch_bits_of_log2(floor_log2(n), floor_log2(m)); }
+// the limit rule (include/eccx.h), n, m > 0
+bool msm_batch_ok(size_t n, size_t m) { return eccx::msm_batch_fits(n, m, msm_batch_window_bits(n, m)); }
+size_t msm_batch_max_bytes(const CurveOps* ops, size_t n, size_t m) {
+  // as msm_max_bytes, over both arguments: the largest (n', m') of each pair of power-of-two ranges decides
+  size_t bytes = 0;
+  for (int lg = 0; lg <= floor_log2(n); ++lg)
+    for (int lgm = 0; lgm <= floor_log2(m); ++lgm) {
+      const size_t n1 = std::min(n, ((size_t)2 << lg) - 1), m1 = std::min(m, ((size_t)2 << lgm) - 1);
+      const int c = msm_batch_bits_of_log2(lg, lgm);
+      if (eccx::msm_batch_fits(n1, m1, c)) bytes = std::max(bytes, ops->msm_batch_bytes(n1, m1, c));
+    }
   return bytes;
 }
 
@@ -1887,6 +1913,91 @@ int eccx_msm(eccx_ctx* ctx, int curve, size_t n, const uint8_t* scalars, const u
   }
   HIP_TRY(ctx, settled(hipMemcpyAsync(out, d_o, pb, hipMemcpyDeviceToHost, s)));
   HIP_TRY(ctx, settled(hipMemcpyAsync(flag, d_f, 1, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
+}
+
+namespace {
+// eccx_msm_batch[_dev] and eccx_msm_batch_reserve: everything checkable before a device is touched
+int msm_batch_args(eccx_ctx* ctx, const CurveOps* ops, size_t n, size_t m, uint32_t opts) {
+  if (!ops->msm_batch) return arg_err(ctx, "eccx_msm_batch: ECCX_BLS12_381_G1 and ECCX_BLS12_381_G2 only");
+  if (opts & ~(uint32_t)ECCX_VALIDATE_POINTS)
+    return arg_err(ctx, "eccx_msm_batch: opts must be 0 or ECCX_VALIDATE_POINTS (bucket addresses are scalar digits: public scalars only)");
+  if (n && m && !msm_batch_ok(n, m))
+    return arg_err(ctx, "eccx_msm_batch: m x n above 2^27, or the list or the key space of this (n, m) leaves 32 bits");
+  return ECCX_OK;
+}
+}  // namespace
+
+int eccx_msm_batch_window_bits(size_t n, size_t m) { return msm_batch_window_bits(n, m); }
+
+int eccx_msm_batch_reserve(eccx_ctx* ctx, int curve, size_t max_n, size_t max_m) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = msm_batch_args(ctx, ops, max_n, max_m, 0)) return rc;
+  if (max_n == 0 || max_m == 0) return ECCX_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return grow(ctx, B_MSMBATCH, msm_batch_max_bytes(ops, max_n, max_m));
+}
+
+int eccx_msm_batch_dev(eccx_ctx* ctx, int curve, size_t n, size_t m, const void* d_scalars, const void* d_points, const void* d_inf,
+                       void* d_out, void* d_flags, uint32_t opts, void* stream) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = msm_batch_args(ctx, ops, n, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_out && d_flags && (n == 0 || (d_scalars && d_points)))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t *out = static_cast<uint8_t*>(d_out), *flags = static_cast<uint8_t*>(d_flags);
+  if (n == 0) {  // m empty sums
+    HIP_TRY(ctx, hipMemsetAsync(out, 0, m * 2 * (size_t)ops->info.fb, s));
+    HIP_TRY(ctx, hipMemsetAsync(flags, ECCX_FLAG_INFINITY, m, s));
+    return ECCX_OK;
+  }
+  // the slab holds every (n', m') below the largest seen (or reserved), as B_MSM does for eccx_msm
+  uint8_t* ws = nullptr;
+  if (int rc = grow(ctx, B_MSMBATCH, msm_batch_max_bytes(ops, n, m), &ws)) return rc;
+  uint32_t* rows = nullptr;
+  HIP_TRY(ctx, ops->msm_batch(s, ctx->cus, n, m, msm_batch_window_bits(n, m), static_cast<const uint8_t*>(d_scalars),
+                              static_cast<const uint8_t*>(d_points), static_cast<const uint8_t*>(d_inf), ws, &rows, flags, kopts_of(opts)));
+  HIP_TRY(ctx, ops->to_affine_add_u(norm_grid(ctx, m), s, m, rows, out, flags));
+  return ECCX_OK;
+}
+
+int eccx_msm_batch(eccx_ctx* ctx, int curve, size_t n, size_t m, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf,
+                   uint8_t* out, uint8_t* flags, uint32_t opts) {
+  const CurveOps* ops;
+  if (int rc = enter(ctx, curve, &ops)) return rc;
+  if (int rc = msm_batch_args(ctx, ops, n, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, out && flags && (n == 0 || (scalars && points)))) return rc;
+  const size_t pb = 2 * (size_t)ops->info.fb, kb = m * n * (size_t)ops->info.sb;
+  // m x n scalars and n records in, m records and flag bytes out, through the I/O slots of the other host forms
+  uint8_t *d_k = nullptr, *d_p = nullptr, *d_i = nullptr, *d_o = nullptr, *d_f = nullptr;
+  int rc = grow(ctx, B_IO + IO_O, m * pb, &d_o);
+  if (!rc) rc = grow(ctx, B_IO + IO_F, m, &d_f);
+  if (!rc && n) rc = grow(ctx, B_IO + IO_K, kb, &d_k);
+  if (!rc && n) rc = grow(ctx, B_IO + IO_P, n * pb, &d_p);
+  if (!rc && n && inf) rc = grow(ctx, B_IO + IO_A, n, &d_i);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  if (n) {
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_k, scalars, kb, hipMemcpyHostToDevice, s)));
+    HIP_TRY(ctx, settled(hipMemcpyAsync(d_p, points, n * pb, hipMemcpyHostToDevice, s)));
+    if (inf) HIP_TRY(ctx, settled(hipMemcpyAsync(d_i, inf, n, hipMemcpyHostToDevice, s)));
+  }
+  rc = eccx_msm_batch_dev(ctx, curve, n, m, d_k, d_p, d_i, d_o, d_f, opts, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  HIP_TRY(ctx, settled(hipMemcpyAsync(out, d_o, m * pb, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, settled(hipMemcpyAsync(flags, d_f, m, hipMemcpyDeviceToHost, s)));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return ECCX_OK;
 }

@@ -43,6 +43,7 @@ int h2c_map_grid_(int cus, size_t n) {
     (t).h2c_map_finish = h2c_map_finish_;                   \
     (t).h2c_map_grid = h2c_map_grid_;                       \
     msm_ops_BLS12_381(t);                                   \
+    msm_batch_ops_BLS12_381(t);                             \
     point_sum_ops_BLS12_381(t);                             \
   } while (0)
 #include "k_weierstrass.inc"

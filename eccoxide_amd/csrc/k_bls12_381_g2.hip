@@ -103,6 +103,7 @@ const CurveOps& ops_BLS12_381_G2() {
     h2c_ops_BLS12_381_G2(t);  // hashing to G2
     pairing_ops_BLS12_381_G2(t);  // the pairing
     point_sum_ops_BLS12_381_G2(t);  // sums of ragged groups
+    msm_batch_ops_BLS12_381_G2(t);  // the batched multi-scalar multiplication (m = 1: the MSM on G2)
     return t;
   }();
   return o;

@@ -410,10 +410,11 @@ inline hipError_t msm_launch_segsum(hipStream_t s, size_t max_len, uint8_t* ws, 
     len = 2 * chunks;
   }
 }
+// (vectors: kernels_msm_batch.hpp runs this over vectors * ceil(257 / c) windows, each of them reduced like any other)
 template <class G>
-inline hipError_t msm_launch_reduce(hipStream_t s, int c, uint8_t* ws, const MsmLayout& L, int* last_pairs) {
+inline hipError_t msm_launch_reduce(hipStream_t s, int c, uint8_t* ws, const MsmLayout& L, int* last_pairs, int vectors = 1) {
   auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-  const int W = msm_windows(c);
+  const int W = msm_windows(c) * vectors;
   uint32_t m = msm_buckets(c);
   for (int level = 0;; ++level) {
     const uint32_t m_out = (m + (1u << MSM_RB) - 1) >> MSM_RB;

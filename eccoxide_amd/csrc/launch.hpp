@@ -216,7 +216,26 @@ struct CurveOps {
   // nothing is read back.  opts: OPT_VALIDATE.
   hipError_t (*point_sum)(hipStream_t s, int cus, size_t n, size_t members, const uint64_t* offsets, const uint8_t* points,
                           const uint8_t* inf, uint32_t* rows, uint8_t* flags, uint32_t opts);
+  // Batched multi-scalar multiplication over shared points (kernels_msm_batch.hpp; bls12_381_g1 and bls12_381_g2, else null):
+  // m results sum_i scalars[g][i] P_i from m x n scalars and n points.  msm_batch enqueues the whole schedule for window
+  // width c on s over a workspace of msm_batch_bytes(n, m, c) bytes (256-byte aligned; sizes are functions of n, m and c
+  // alone, nothing is read back) and leaves m homogeneous rows for to_affine_add_u at *rows, inside the workspace, and 0 / 2
+  // (a rejected term: every sum) in flags.  The caller keeps (n, m, c) inside msm_batch_fits below.  opts: OPT_VALIDATE.
+  size_t (*msm_batch_bytes)(size_t n, size_t m, int c);
+  hipError_t (*msm_batch)(hipStream_t s, int cus, size_t n, size_t m, int c, const uint8_t* scalars, const uint8_t* points,
+                          const uint8_t* inf, uint8_t* ws, uint32_t** rows, uint8_t* flags, uint32_t opts);
 };
+// The limit rule of the batched multi-scalar multiplication for n, m > 0 at window width c, with W = ceil(257 / c) windows
+// of B = 2^(c-1) buckets: m x n units at most 2^27 (term | sign << 31 and the unit index stay inside 32 bits), and the list
+// (W x m x n slots) and the key space (m x W x B) at most 2^32 - 2^12 (the scan's tiles and the chunking round up inside 32
+// bits).
+inline bool msm_batch_fits(size_t n, size_t m, int c) {
+  constexpr size_t MAX_UNITS = (size_t)1 << 27;
+  constexpr uint64_t MAX_U32 = 0xFFFFF000ull;
+  if (m > MAX_UNITS || n > MAX_UNITS / m) return false;
+  const uint64_t W = (uint64_t)((257 + c - 1) / c), B = (uint64_t)1 << (c - 1), units = (uint64_t)m * n;
+  return W * units <= MAX_U32 && W * B * (uint64_t)m <= MAX_U32;
+}
 // units normalised per lane with one inversion: 16 where the prefix products fit the register
 // file (8-limb fields), 8 above
 constexpr int to_affine_u(int limbs) { return limbs <= 8 ? ECCX_NORM_U8 : ECCX_NORM_UBIG; }
@@ -240,6 +259,8 @@ const CurveOps& ops_JUBJUB();  // k_jubjub.hip: the Edwards templates on Fr; no 
 const CurveOps& ops_BLS12_381_G2();  // kernels_g2.hpp: no reference-mirroring slots (var, base, point_add are null)
 void h2c_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_h2c.hip: the h2c_* slots of ops_BLS12_381_G2
 void msm_ops_BLS12_381(CurveOps& t);  // k_bls12_381_msm.hip: the msm slots of ops_BLS12_381
+void msm_batch_ops_BLS12_381(CurveOps& t);     // k_bls12_381_msm_batch.hip: the msm_batch slots of ops_BLS12_381 ...
+void msm_batch_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_g2_msm_batch.hip: ... and of ops_BLS12_381_G2
 void pairing_ops_BLS12_381_G2(CurveOps& t);  // k_bls12_381_pairing.hip: the pairing_* slots of ops_BLS12_381_G2
 void point_sum_ops_BLS12_381(CurveOps& t);     // k_bls12_381_sig.hip: the point_sum slot of ops_BLS12_381 ...
 void point_sum_ops_BLS12_381_G2(CurveOps& t);  // ... and of ops_BLS12_381_G2

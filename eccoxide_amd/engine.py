@@ -286,6 +286,29 @@ class Engine:
         self._check(rc)
         return out.raw, flag.raw[0]
 
+    def msm_batch(self, curve, scalars: bytes, points: bytes, m: int, *, inf: Optional[bytes] = None, validate: bool = False):
+        """Batched multi-scalar multiplication over shared points (eccx_msm_batch; curves "bls12_381_g1" and
+        "bls12_381_g2"; PUBLIC scalars only): out[g] = sum_i scalars[g][i] * points[i] for g < m.  scalars: m x n x 32
+        big-endian, vector-major, any 256-bit integers; points: n affine records (96 or 192 bytes), in the prime-order
+        subgroup or not; inf: n flag bytes shared by all vectors (1: the term contributes nothing, 2: rejects every sum).
+        Returns (m records, m flags): 0 a point, 1 the point at infinity, 2 rejected."""
+        cid = curve_id(curve)
+        sb, fb = scalar_bytes(cid), field_bytes(cid)
+        m = int(m)
+        if m < 0 or len(points) % (2 * fb):
+            raise ValueError("points length is not a multiple of the record size")
+        n = len(points) // (2 * fb)
+        if len(scalars) != m * n * sb:
+            raise ValueError("scalars must hold m x n scalars")
+        if inf is not None and len(inf) != n:
+            raise ValueError("inf must hold one flag byte per term")
+        out = ctypes.create_string_buffer(max(1, m * 2 * fb))
+        flags = ctypes.create_string_buffer(max(1, m))
+        rc = self._lib.eccx_msm_batch(self._ctx, cid, n, m, scalars if (n and m) else None, points if n else None, inf if n else None,
+                                      out, flags, VALIDATE_POINTS if validate else 0)
+        self._check(rc)
+        return out.raw[: m * 2 * fb], flags.raw[:m]
+
     def point_sum(self, curve, points: bytes, offsets, *, inf: Optional[bytes] = None, validate: bool = False):
         """One sum per ragged group of points (eccx_point_sum; curves "bls12_381_g1" and "bls12_381_g2"): group g is the
         records offsets[g] - offsets[0] .. offsets[g + 1] - offsets[0] of `points` (affine x || y records, in the
@@ -677,6 +700,14 @@ class Engine:
     def msm_window_bits(self, n: int) -> int:
         """The window width msm uses for n terms (a pure function of n)."""
         return int(self._lib.eccx_msm_window_bits(int(n)))
+
+    def msm_batch_window_bits(self, n: int, m: int) -> int:
+        """The window width msm_batch uses for m vectors of n terms (a pure function of both)."""
+        return int(self._lib.eccx_msm_batch_window_bits(int(n), int(m)))
+
+    def reserve_msm_batch(self, curve, max_n: int, max_m: int):
+        """eccx_msm_batch_reserve: size the workspace of msm_batch / msm_batch_t for every n <= max_n and m <= max_m."""
+        self._check(self._lib.eccx_msm_batch_reserve(self._ctx, curve_id(curve), int(max_n), int(max_m)))
 
     def double_scalarmul(self, curve, u1: bytes, u2: bytes, q: bytes, *, subtract: bool = False,
                          validate: bool = False, x_only: bool = False):
@@ -1349,6 +1380,31 @@ class Engine:
                                     VALIDATE_POINTS if validate else 0, stream)
         self._check(rc)
         return out, flag
+
+    def msm_batch_t(self, curve, scalars, points, m: int, out=None, flags=None, *, inf=None, validate: bool = False,
+                    stream: Optional[int] = None):
+        """Device-tensor form of msm_batch (torch.uint8 CUDA tensors): scalars m x n x 32, points n x 2FB, inf n; out
+        (m x 2FB) and flags (m) receive the m sums; enqueued on the stream, nothing is synchronised."""
+        import torch
+
+        cid = curve_id(curve)
+        sb, fb = scalar_bytes(cid), field_bytes(cid)
+        m = int(m)
+        n = self._units(points, 2 * fb, "points")
+        if out is None:
+            out = torch.empty((m * 2 * fb,), dtype=torch.uint8, device=points.device)
+        if flags is None:
+            flags = torch.empty((m,), dtype=torch.uint8, device=points.device)
+        self._tensors(n, ("points", points, 2 * fb), ("inf", inf, 1))
+        self._tensors(m, ("scalars", scalars, n * sb), ("out", out, 2 * fb), ("flags", flags, 1))
+        if stream is None:
+            stream = torch.cuda.current_stream(points.device).cuda_stream
+        live = n > 0 and m > 0
+        rc = self._lib.eccx_msm_batch_dev(self._ctx, cid, n, m, scalars.data_ptr() if live else None, points.data_ptr() if n else None,
+                                          inf.data_ptr() if (inf is not None and n) else None, out.data_ptr(), flags.data_ptr(),
+                                          VALIDATE_POINTS if validate else 0, stream)
+        self._check(rc)
+        return out, flags
 
     def point_sum_t(self, curve, points, offsets, out=None, flags=None, *, inf=None, validate: bool = False,
                     stream: Optional[int] = None):

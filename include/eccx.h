@@ -665,6 +665,41 @@ int eccx_msm_dev(eccx_ctx* ctx, int curve, size_t n, const void* d_scalars, cons
 /* The window width c (bits) eccx_msm uses for n terms: ceil(257 / c) windows of 2^(c-1) buckets.  Non-decreasing in n. */
 int eccx_msm_window_bits(size_t n);
 
+/* Batched multi-scalar multiplication over SHARED points: out[g] = sum_{i<n} scalars[g][i] * points[i] for g < m -- m
+ * polynomials committed against one SRS, an EIP-4844 blob's 4096 scalars against 4096 points.  The schedule of eccx_msm runs
+ * over m x W windows at once, so the serial chains that make up a single call's floor are paid once per batch.
+ *   curve   : ECCX_BLS12_381_G1 or ECCX_BLS12_381_G2 (m == 1 there is the multi-scalar multiplication on G2); any other valid
+ *             id is ECCX_ERR_ARG, an invalid one ECCX_ERR_CURVE
+ *   scalars : m x n x 32 big-endian, vector-major (vector g is scalars + g * n * 32), each any 256-bit integer
+ *   points  : n affine x || y records of 96 (G1) or 192 (G2) bytes, as eccx_msm and eccx_point_sum take them: any point of
+ *             the curve, in the prime-order subgroup or not
+ *   inf     : NULL or n flag bytes shared by all vectors: 1 -- the term contributes nothing to any sum, whatever its
+ *             coordinate bytes are; 2 -- rejects every sum
+ *   out     : m records; flags: m bytes, with eccx_msm's values: 0, ECCX_FLAG_INFINITY (zero bytes), ECCX_FLAG_REJECTED (zero
+ *             bytes)
+ *   opts    : 0 or ECCX_VALIDATE_POINTS (a point not flagged 1 with a coordinate >= p or off the curve rejects every sum).
+ *             Every other bit is ECCX_ERR_ARG, returned before anything is launched or written; that includes ECCX_CT_SCAN,
+ *             for eccx_msm's reason: PUBLIC scalars only.
+ * m == 0 returns ECCX_OK and writes nothing.  n == 0 with m > 0 writes the point at infinity to every out; out and flags
+ * are required, the other pointers may be NULL.  Otherwise a null scalars, points, out or flags is ECCX_ERR_ARG.
+ * Size limits (ECCX_ERR_ARG before anything is launched), for n, m > 0 with c = eccx_msm_batch_window_bits(n, m) and
+ * W = ceil(257 / c): refused when m * n > 2^27, or W * m * n > 2^32 - 2^12 (the sorted list's slots), or
+ * m * W * 2^(c-1) > 2^32 - 2^12 (the sort's key space).
+ * Every size and launch is a function of (n, m) alone and nothing is read back.  The _dev form enqueues on `stream` and
+ * returns; after eccx_msm_batch_reserve(ctx, curve, N, M) a call with n <= N and m <= M neither allocates, frees nor
+ * synchronises.  The workspace is the context's, a slot of its own beside eccx_msm's, and grow-only.  The same input gives
+ * the same bytes; on G1 with m == 1 they are eccx_msm's. */
+int eccx_msm_batch(eccx_ctx* ctx, int curve, size_t n, size_t m, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf,
+                   uint8_t* out, uint8_t* flags, uint32_t opts);
+int eccx_msm_batch_dev(eccx_ctx* ctx, int curve, size_t n, size_t m, const void* d_scalars, const void* d_points, const void* d_inf,
+                       void* d_out, void* d_flags, uint32_t opts, void* stream);
+/* The window width c (bits) eccx_msm_batch uses for m vectors of n terms: a pure function of (floor(log2 n), floor(log2 m))
+ * inside 4 .. 16, non-decreasing in n for fixed m, and eccx_msm_window_bits(n) at m == 1. */
+int eccx_msm_batch_window_bits(size_t n, size_t m);
+/* Sizes the workspace of eccx_msm_batch_dev for every n <= max_n and m <= max_m inside the size limits (the limits apply to
+ * (max_n, max_m) itself: ECCX_ERR_ARG). */
+int eccx_msm_batch_reserve(eccx_ctx* ctx, int curve, size_t max_n, size_t max_m);
+
 /* Sums of ragged groups of points: ONE result per GROUP, out[g] = the sum of the group's members -- what aggregating the
  * public keys of a committee (BLS FastAggregateVerify) or a set of signatures takes.  eccx_point_add makes one result
  * per pair and eccx_msm one per call; here each group is summed by one wavefront, or by one lane where it has at most 7

@@ -210,6 +210,14 @@ extern "C" {
                         d_inf: *const c_void, d_out: *mut c_void, d_flag: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
     pub fn eccx_msm_window_bits(n: usize) -> c_int;
 
+    // m results sum_i scalars[g][i] * points[i] over SHARED points on BLS12-381 G1 or G2 (public scalars only)
+    pub fn eccx_msm_batch(ctx: *mut eccx_ctx, curve: c_int, n: usize, m: usize, scalars: *const u8, points: *const u8, inf: *const u8,
+                          out: *mut u8, flags: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_msm_batch_dev(ctx: *mut eccx_ctx, curve: c_int, n: usize, m: usize, d_scalars: *const c_void, d_points: *const c_void,
+                              d_inf: *const c_void, d_out: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    pub fn eccx_msm_batch_window_bits(n: usize, m: usize) -> c_int;
+    pub fn eccx_msm_batch_reserve(ctx: *mut eccx_ctx, curve: c_int, max_n: usize, max_m: usize) -> c_int;
+
     // ONE sum per ragged group of points on BLS12-381 G1 or G2: aggregating public keys or signatures
     pub fn eccx_point_sum(ctx: *mut eccx_ctx, curve: c_int, n: usize, offsets: *const u64, members: usize, points: *const u8,
                           inf: *const u8, out: *mut u8, flags: *mut u8, opts: u32) -> c_int;

@@ -33,3 +33,25 @@ pub fn msm(gpu: &GpuContext, scalars: &[u8], points: &[u8], validate: bool) -> R
 pub fn window_bits(n: usize) -> i32 {
     unsafe { ffi::eccx_msm_window_bits(n) }
 }
+
+/// Batched multi-scalar multiplication over SHARED points (`eccx_msm_batch`) on BLS12-381 G1 or G2: `out[g] = sum_i
+/// scalars[g][i] * points[i]` for g < m -- m polynomials committed against one SRS.  `scalars` is m x n x 32 bytes,
+/// vector-major; `points` is n records of 96 bytes on G1 and 192 on G2 (`g2`).  Returns the m records (zero bytes where the
+/// flag is not `ECCX_FLAG_FINITE`) and the m flags.
+pub fn msm_batch(gpu: &GpuContext, g2: bool, m: usize, scalars: &[u8], points: &[u8], validate: bool) -> Result<(Vec<u8>, Vec<u8>), GpuError> {
+    let (curve, pb) = if g2 { (ffi::ECCX_BLS12_381_G2, 2 * POINT_BYTES) } else { (Curve::Bls12381G1.id(), POINT_BYTES) };
+    assert!(points.len() % pb == 0 && scalars.len() == m * (points.len() / pb) * 32);
+    let n = points.len() / pb;
+    let (mut out, mut flags) = (vec![0u8; m * pb], vec![0u8; m]);
+    let opts = if validate { ffi::ECCX_VALIDATE_POINTS } else { 0 };
+    let (k, p) = if n == 0 || m == 0 { (core::ptr::null(), core::ptr::null()) } else { (scalars.as_ptr(), points.as_ptr()) };
+    gpu.check(unsafe {
+        ffi::eccx_msm_batch(gpu.raw(), curve, n, m, k, p, core::ptr::null(), out.as_mut_ptr(), flags.as_mut_ptr(), opts)
+    })?;
+    Ok((out, flags))
+}
+
+/// The window width `msm_batch` uses for m vectors of n terms.
+pub fn batch_window_bits(n: usize, m: usize) -> i32 {
+    unsafe { ffi::eccx_msm_batch_window_bits(n, m) }
+}
