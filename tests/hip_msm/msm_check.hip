@@ -5,6 +5,7 @@
 //                     from the product's own conversion kernel; every bucket row comes back normalised
 //   msmcheck_reduce   the window reduction sum_j j B_j on bucket rows it is given (affine points, present or not), one
 //                     normalised point per window
+//   msmcheck_msm_host the whole schedule on host buffers with the grid caps of a card of the caller's compute-unit count
 // Bucket rows and window sums go through the product's batched normalisation.  Not part of the product; built by
 // __graft_entry__.build().
 #include <hip/hip_runtime.h>
@@ -181,4 +182,33 @@ extern "C" int msmcheck_msm_dev(size_t n, int c, const void* d_scalars, const vo
   hipLaunchKernelGGL((k_batch_to_affine_unsat<CU, NORM_HOMOGENEOUS, 8>), dim3(1), dim3(WG), 0, s, (size_t)1, row, static_cast<uint8_t*>(d_out),
                      static_cast<uint8_t*>(d_flag));
   return (int)hipGetLastError();
+}
+
+// The whole schedule on HOST buffers with the prepare and scatter grids capped as on a card of `cus` compute units
+// (msm_grid(n, cus * 8): with cus = 1, 8 workgroups, 2048 lanes), so that a few thousand terms walk the grid-stride loop
+// more than once.  inf: null or n flags; out: 96 bytes; flag: 1 byte.  It allocates, copies and synchronises.
+extern "C" int msmcheck_msm_host(int cus, size_t n, int c, const uint8_t* scalars, const uint8_t* points, const uint8_t* inf, uint8_t* out,
+                                 uint8_t* flag) {
+  using namespace eccx;
+  if (cus < 1 || n == 0 || n > MSM_MAX_N || c < MSM_MIN_BITS || c > MSM_MAX_BITS || !scalars || !points || !out || !flag) return -1;
+  const size_t bytes = msm_layout<G>(n, c).bytes;
+  Dev d;
+  uint8_t* d_k = d.get<uint8_t>(n * 32, scalars);
+  uint8_t* d_p = d.get<uint8_t>(n * G::POINT_BYTES, points);
+  uint8_t* d_inf = inf ? d.get<uint8_t>(n, inf) : nullptr;
+  uint8_t* ws = d.get<uint8_t>(bytes);
+  uint8_t* d_out = d.get<uint8_t>(G::POINT_BYTES);
+  uint8_t* d_fl = d.get<uint8_t>(1);
+  if (d.e == hipSuccess) d.e = hipMemset(ws, 0xA5, bytes);  // junk wherever the schedule does not write first
+  if (d.e != hipSuccess) return (int)d.e;
+  uint32_t* row = nullptr;
+  hipError_t e = msm_launch<G>(nullptr, cus, n, c, d_k, d_p, d_inf, ws, &row, d_fl, false);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_batch_to_affine_unsat<CU, NORM_HOMOGENEOUS, 8>), dim3(1), dim3(WG), 0, nullptr, (size_t)1, row, d_out, d_fl);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, G::POINT_BYTES, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(flag, d_fl, 1, hipMemcpyDeviceToHost);
+  return (int)e;
 }

@@ -5,6 +5,7 @@
 //   msmbcheck_bytes   the workspace of one (n, m, c)
 //   msmbcheck_dev     the whole schedule and the curve's normalisation on DEVICE buffers and a stream, without synchronising
 //   msmbcheck_host    the same on host buffers (it allocates, copies and synchronises)
+//   msmbcheck_host_cus  msmbcheck_host with the grid caps of a card of the caller's compute-unit count
 // Not part of the product; built by __graft_entry__.build().
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -73,10 +74,12 @@ extern "C" int msmbcheck_dev(int g2, size_t n, size_t m, int c, const void* d_sc
                   static_cast<uint8_t*>(d_out), static_cast<uint8_t*>(d_flags));
 }
 
-extern "C" int msmbcheck_host(int g2, size_t n, size_t m, int c, const uint8_t* scalars, const uint8_t* points, uint8_t* out, uint8_t* flags) {
+// msmbcheck_host_cus: the grids capped as on a card of `cus` compute units (cus = 1: the prepare passes run 8 workgroups,
+// 2048 lanes, and Horner 8 workgroups of 64 lanes), so that small batches walk the grid-stride loops more than once
+extern "C" int msmbcheck_host_cus(int g2, int cus, size_t n, size_t m, int c, const uint8_t* scalars, const uint8_t* points, uint8_t* out,
+                                  uint8_t* flags) {
   using namespace eccx;
   if (!fits(n, m, c) || !scalars || !points || !out || !flags) return -1;
-  const int cus = cus_of_device();
   if (cus <= 0) return -1;
   const size_t pb = g2 ? G2P::POINT_BYTES : G1P::POINT_BYTES, bytes = msmbcheck_bytes(g2, n, m, c);
   uint8_t *d_k = nullptr, *d_p = nullptr, *d_ws = nullptr, *d_o = nullptr, *d_f = nullptr;
@@ -94,4 +97,8 @@ extern "C" int msmbcheck_host(int g2, size_t n, size_t m, int c, const uint8_t* 
   if (e == hipSuccess) e = hipMemcpy(flags, d_f, m, hipMemcpyDeviceToHost);
   for (void* q : {(void*)d_k, (void*)d_p, (void*)d_ws, (void*)d_o, (void*)d_f}) (void)hipFree(q);
   return (int)e;
+}
+
+extern "C" int msmbcheck_host(int g2, size_t n, size_t m, int c, const uint8_t* scalars, const uint8_t* points, uint8_t* out, uint8_t* flags) {
+  return msmbcheck_host_cus(g2, eccx::cus_of_device(), n, m, c, scalars, points, out, flags);
 }

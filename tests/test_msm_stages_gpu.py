@@ -1,6 +1,8 @@
 """The stages of the multi-scalar multiplication each on its own, through tests/hip_msm/libmsmcheck.so: the recoding kernel
 against the model's recoding, the segmented sum on grouped lists made up here (so a wrong sum cannot hide behind a wrong
-sort), and the window reduction on bucket rows made up here (empty buckets hold junk), against tests/msm_ref.py."""
+sort), and the window reduction on bucket rows made up here (empty buckets hold junk), against tests/msm_ref.py.  Last,
+the whole schedule with the grids capped as on a card of ONE compute unit, so that 2348 terms walk the prepare and scatter
+kernels' grid-stride loop twice, the second time ragged."""
 import ctypes
 import os
 import random
@@ -32,6 +34,9 @@ def lib():
                                   ctypes.c_void_p, ctypes.c_void_p]
     h.msmcheck_reduce.restype = ctypes.c_int
     h.msmcheck_reduce.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
+    h.msmcheck_msm_host.restype = ctypes.c_int
+    h.msmcheck_msm_host.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                    ctypes.c_void_p, ctypes.c_void_p]
     return h
 
 
@@ -125,3 +130,57 @@ def test_window_reduction(lib, c):
     for win in range(w):
         total = sum((j + 1) * mult[win * b + j] for j in range(b)) % R
         assert (out.raw[96 * win:96 * win + 96], fl.raw[win]) == M.record(M.R.affine_mul(M.C, total, M.G)), (c, win)
+
+
+# ---- the whole schedule on a grid capped at 8 workgroups ---------------------------------------------------------------
+CAP_LANES = 8 * 256          # msm_grid(n, cus * 8) at cus = 1
+SMALL_N = CAP_LANES + 300    # the second trip: one full workgroup, then 44 lanes of a wave and 212 lanes clamped to n - 1
+RUN = range(CAP_LANES - 35, CAP_LANES + 35)  # 70 equal scalars: one bucket per window filled from both trips
+
+
+@pytest.fixture(scope="module")
+def small_grid_case():
+    """SMALL_N distinct points r_i G (the fixed-base kernel makes them; the multipliers stay here) and random 256-bit
+    scalars, shared by every width"""
+    import eccoxide_amd as E
+
+    rng = random.Random(2348)
+    rs = [rng.randrange(1, R) for _ in range(SMALL_N)]
+    ks = [rng.randrange(1 << 256) for _ in range(SMALL_N)]
+    same = rng.randrange(1 << 256)
+    for i in RUN:
+        ks[i] = same
+    with E.Engine(0) as eng:
+        recs, fl = eng.scalarmul_base("bls12_381_g1", b"".join(r.to_bytes(32, "big") for r in rs))
+    assert fl == bytes(SMALL_N)
+    return rs, ks, recs
+
+
+@pytest.mark.parametrize("tail", ["flagged", "live"])
+@pytest.mark.parametrize("c", range(M.MIN_BITS, M.MAX_BITS + 1))
+def test_second_ragged_trip_on_one_cu(lib, small_grid_case, c, tail):
+    """cus = 1: units 2048 .. 2347 are the second trip of k_msm_prepare<G, false / true>; its last workgroup holds 44 units,
+    so one wave enters msm_wave_slot with 20 lanes past n and three waves with all 64.
+    flagged: the last 44 terms are flagged 1 -- the partial wave's own units must file nothing.
+    live:    the 44 flagged terms are the ones before them and the tail is live, so the partial wave ranks real entries
+             beside its clamped lanes, and the clamped lanes' unit n - 1 is a live term: a clamped lane that files it is a
+             wrong sum.  (Under `flagged` unit n - 1 is dead whoever reads it, so that shape alone cannot see such a lane.)
+             k[n - 1] = 3, one nonzero digit at every width."""
+    rs, ks, recs = small_grid_case
+    ks, inf = list(ks), bytearray(SMALL_N)
+    dead = range(SMALL_N - 44, SMALL_N) if tail == "flagged" else range(SMALL_N - 88, SMALL_N - 44)
+    for i in dead:
+        inf[i] = 1
+    if tail == "live":
+        ks[SMALL_N - 1] = 3
+    assert len(RUN) == 70 and RUN[0] < CAP_LANES <= RUN[-1] and not set(RUN) & set(dead)
+    want = M.record(M.msm_of_multiples([k for i, k in enumerate(ks) if not inf[i]], [r for i, r in enumerate(rs) if not inf[i]]))
+    out, fl = ctypes.create_string_buffer(b"\xaa" * 96, 96), ctypes.create_string_buffer(b"\xaa", 1)
+    assert lib.msmcheck_msm_host(1, SMALL_N, c, b"".join(k.to_bytes(32, "big") for k in ks), recs, bytes(inf), out, fl) == 0
+    assert (out.raw, fl.raw[0]) == want, (c, tail)
+
+
+def test_small_grid_bad_arguments(lib):
+    buf = ctypes.create_string_buffer(96)
+    for cus, n, c in ((0, 1, 4), (1, 0, 4), (1, 1, 3), (1, 1, 17)):
+        assert lib.msmcheck_msm_host(cus, n, c, buf, buf, None, buf, buf) == -1
