@@ -99,6 +99,16 @@ SYMBOLS = {
                                       c_uint32]),
     "eccx_bls_batch_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, _u8p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_kzg_eval": (c_int, [c_void_p, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_kzg_eval_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_kzg_commit": (c_int, [c_void_p, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_kzg_commit_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "eccx_kzg_open": (c_int, [c_void_p, c_size_t, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_kzg_open_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_uint32, c_void_p]),
+    "eccx_kzg_verify": (c_int, [c_void_p, c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, c_uint32]),
+    "eccx_kzg_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, _u8p, c_void_p, c_uint32, c_void_p]),
+    "eccx_kzg_reserve": (c_int, [c_void_p, c_size_t, c_size_t]),
     "eccx_comb_table": (c_int, [c_void_p, c_int, _u8p]),
     "eccx_scalarmul_var_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, _u8p, c_uint32]),
     "eccx_scalarmul_base_sharded": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t, _u8p, _u8p, _u8p, c_uint32]),

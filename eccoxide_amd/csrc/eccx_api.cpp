@@ -60,8 +60,9 @@ const CurveOps* ops_of(int curve) {
 //   B_BLS      the working slab of the eccx_bls_* entry points (BlsSlab below)
 //   B_BLSAGG   the working slab of eccx_bls_aggregate_verify (BlsAggSlab below)
 //   B_BLSBATCH the working slab of eccx_bls_batch_verify (BlsBatchSlab below)
+//   B_KZG      the working slab of the eccx_kzg_* entry points (KzgPolySlab and KzgVerifySlab below)
 enum { IO_K = 0, IO_P = 1, IO_O = 2, IO_F = 3, IO_J = 4, IO_A = 5, IO_B = 6, NIO = 7 };
-enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, B_BLSBATCH, B_MSMBATCH, NBUF };
+enum { B_SCRATCH, B_ROWS, B_IO, B_ECDSA = B_IO + NIO, B_ED, B_EDSIGN, B_ECSIGN, B_MSM, B_BLS, B_BLSAGG, B_BLSBATCH, B_MSMBATCH, B_KZG, NBUF };
 struct DevBuf {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -689,6 +690,64 @@ size_t msm_batch_max_bytes(const CurveOps* ops, size_t n, size_t m) {
 
 uint32_t kopts_of(uint32_t opts) { return (opts & ECCX_VALIDATE_POINTS) ? K_VALIDATE : 0u; }
 
+// ---- KZG: the shapes served, the working slabs and what eccx_kzg_reserve / ECCX_PREP_KZG size ------------------------------
+// m polynomials of N evaluations: N a power of two up to 2^20, m x N up to 2^27 and inside eccx_msm_batch's limits
+constexpr size_t KZG_MAX_N = (size_t)1 << 20, KZG_MAX_UNITS = (size_t)1 << 27;
+const char* kzg_shape_err(size_t N, size_t m) {
+  if (m == 0) return nullptr;
+  if (N == 0 || (N & (N - 1)) != 0 || N > KZG_MAX_N) return "eccx_kzg: N must be a power of two, 1 .. 2^20";
+  if (m > KZG_MAX_UNITS / N || !msm_batch_ok(N, m)) return "eccx_kzg: m x N above 2^27";
+  return nullptr;
+}
+// the polynomial entry points: the Fr kernels' workspace (prefix products, then inverses: 36 bytes per evaluation), the
+// quotients (m x N x 32, eccx_kzg_open alone), the range test's flags (m), the sum's record and flag (m x 96, m)
+struct KzgPolySlab {
+  uint8_t *ws, *quot, *pre, *sum, *sum_fl;
+  static KzgPolySlab lay(Carve& c, size_t N, size_t m, bool quot) {
+    return {c.take(eccx::kzg_workspace_bytes(N, m)), c.take(quot ? m * N * 32 : 0), c.take(m), c.take(m * 96), c.take(m)};
+  }
+};
+// eccx_kzg_verify, n openings: the decoded commitments and proofs (n x 96 each) with their flags, the ladder's scalars
+// u1 = -y, u2 = z (n x 32 each), T = [u1]G1 + [u2]pi and A = C + T (n x 96 each) with theirs, the pairing's unit-major terms,
+// pairs = 2 (g1 n x 192, g2 n x 384) with their infinity flags (2n each), the pairing's verdicts (n)
+struct KzgVerifySlab {
+  uint8_t *c, *c_fl, *p, *p_fl, *u1, *u2, *t, *t_fl, *a, *a_fl, *g1, *g2, *g1_inf, *g2_inf, *pv;
+  static KzgVerifySlab lay(Carve& c, size_t n) {
+    return {c.take(n * 96), c.take(n), c.take(n * 96), c.take(n), c.take(n * 32), c.take(n * 32), c.take(n * 96), c.take(n),
+            c.take(n * 96), c.take(n), c.take(n * 192), c.take(n * 384), c.take(2 * n), c.take(2 * n), c.take(n)};
+  }
+};
+// out == nullptr: only size the slab
+int ensure_kzg_poly_slab(eccx_ctx* ctx, size_t N, size_t m, bool quot, KzgPolySlab* out) {
+  Carve size{nullptr};
+  KzgPolySlab::lay(size, N, m, quot);
+  uint8_t* base = nullptr;
+  const int rc = grow(ctx, B_KZG, size.end, &base);
+  if (rc || !out) return rc;
+  Carve c{base};
+  *out = KzgPolySlab::lay(c, N, m, quot);
+  return ECCX_OK;
+}
+int ensure_kzg_verify_slab(eccx_ctx* ctx, size_t n, KzgVerifySlab* out) {
+  Carve size{nullptr};
+  KzgVerifySlab::lay(size, n);
+  uint8_t* base = nullptr;
+  const int rc = grow(ctx, B_KZG, size.end, &base);
+  if (rc || !out) return rc;
+  Carve c{base};
+  *out = KzgVerifySlab::lay(c, n);
+  return ECCX_OK;
+}
+// what eccx_kzg_verify_dev touches beside its slab for n openings: the fused ladder's table slab and rows on G1 (the group
+// law's rows are the same buffer) and the pairing at pairs = 2
+int reserve_kzg_verify(eccx_ctx* ctx, size_t n) {
+  const CurveOps *g1 = ops_of(ECCX_BLS12_381_G1), *g2 = ops_of(ECCX_BLS12_381_G2);
+  int rc = ensure_kzg_verify_slab(ctx, n, nullptr);
+  if (!rc) rc = ensure_work(ctx, g1, n, {need_var_fast(ctx, g1, n), g1->var_coz_fused ? need_var_coz_fused(ctx, g1, n) : Need{0, 0}});
+  if (!rc) rc = ensure_pairing(ctx, need_pairing(ctx, g2, n, 2));
+  return rc;
+}
+
 size_t proj_bytes(const CurveOps* ops) { return (size_t)(ops->info.edwards ? 4 : 3) * ops->info.fb; }
 
 // ---- host-buffer entry points: copies in, kernels, copies out ------------------------------------------------
@@ -1107,6 +1166,8 @@ int eccx_reserve(eccx_ctx* ctx, int curve, size_t max_n, uint32_t what) {
     if (!rc) rc = ensure_pairing_groups(ctx, need_pairing_groups(ctx, g2, max_n, max_n));
     if (!rc && (what & ECCX_PREP_HOST)) rc = bls_batch_host_slots(ctx, max_n, max_n, 96, 96, nullptr);
   }
+  // eccx_kzg_verify for max_n openings (the polynomial entry points have two sizes: eccx_kzg_reserve)
+  if (!rc && (what & ECCX_PREP_KZG)) rc = reserve_kzg_verify(ctx, max_n);
   // eccx_hash_to_g1 and eccx_hash_to_g2 work in the result rows alone, which ensure_work sized above (ECCX_PREP_H2C: two
   // rows per unit on bls12_381_g2, nothing more on bls12_381_g1)
   return rc;
@@ -2525,6 +2586,185 @@ int eccx_bls_batch_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const ui
   if (n && member_status) HIP_TRY(ctx, settled(hipMemcpyAsync(member_status, io.status, n, hipMemcpyDeviceToHost, s)));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return ECCX_OK;
+}
+
+namespace {
+// eccx_kzg_*: everything checkable before a device is touched
+int kzg_args(eccx_ctx* ctx, size_t N, size_t m, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts) return arg_err(ctx, "eccx_kzg: opts must be 0");
+  if (const char* e = kzg_shape_err(N, m)) return arg_err(ctx, e);
+  return ECCX_OK;
+}
+// N^-1 mod r for N = 2^k dividing r - 1: N (r - 1) / N = -1, so the inverse is r - (r - 1) / N.  32 big-endian bytes.
+void kzg_ninv(size_t N, uint8_t (&out)[32]) {
+  static const uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+  const int k = floor_log2(N);
+  uint32_t q[8], t[8];
+  for (int i = 0; i < 8; ++i) t[i] = R[i];
+  t[0] -= 1;  // r is odd
+  for (int i = 0; i < 8; ++i) q[i] = k == 0 ? t[i] : (t[i] >> k) | (i + 1 < 8 ? t[i + 1] << (32 - k) : 0u);
+  uint64_t borrow = 0;
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t d = (uint64_t)R[i] - q[i] - borrow;
+    borrow = (d >> 32) & 1u;
+    const uint32_t w = (uint32_t)d;
+    for (int b = 0; b < 4; ++b) out[31 - 4 * i - b] = (uint8_t)(w >> (8 * b));
+  }
+}
+
+// eccx_kzg_eval_dev, and eccx_kzg_open_dev where d_srs is given: the Fr kernel, then for the proofs the batched
+// multi-scalar multiplication of the quotients against the setup, the compressor and the zeroing of refused polynomials
+int kzg_open_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_zs, const void* d_domain, const void* d_srs,
+                 void* d_ys, void* d_proofs, void* d_flags, bool open, uint32_t opts, void* stream) {
+  if (int rc = kzg_args(ctx, N, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_polys && d_zs && d_domain && d_ys && d_flags && (!open || (d_srs && d_proofs)))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  KzgPolySlab b;
+  if (int rc = ensure_kzg_poly_slab(ctx, N, m, open, &b)) return rc;
+  uint8_t ninv[32];
+  kzg_ninv(N, ninv);
+  uint8_t* flags = static_cast<uint8_t*>(d_flags);
+  HIP_TRY(ctx, eccx::launch_kzg_eval_quotient(s, N, m, static_cast<const uint8_t*>(d_polys), static_cast<const uint8_t*>(d_zs),
+                                              static_cast<const uint8_t*>(d_domain), ninv, reinterpret_cast<uint32_t*>(b.ws),
+                                              static_cast<uint8_t*>(d_ys), open ? b.quot : nullptr, open ? b.pre : flags));
+  if (!open) return ECCX_OK;
+  // a refused polynomial's quotient is zero bytes: its sum is the identity, and k_kzg_finish zeroes its encoding
+  if (int rc = eccx_msm_batch_dev(ctx, ECCX_BLS12_381_G1, N, m, b.quot, d_srs, nullptr, b.sum, b.sum_fl, 0, s)) return rc;
+  if (int rc = eccx_point_compress_dev(ctx, ECCX_BLS12_381_G1, m, b.sum, b.sum_fl, d_proofs, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_kzg_finish(s, m, b.pre, b.sum_fl, static_cast<uint8_t*>(d_proofs), 48, flags));
+  return ECCX_OK;
+}
+
+// device copies of the polynomial entry points' host forms: one slot per argument, copied whole on the context's stream
+struct KzgHostArg {
+  int slot;
+  const uint8_t* in;
+  uint8_t* out;
+  size_t bytes;
+  uint8_t* dev;
+};
+extern "C++" template <int NB, class Launch>
+int kzg_host(eccx_ctx* ctx, KzgHostArg (&args)[NB], Launch launch) {
+  for (KzgHostArg& a : args)
+    if (int rc = grow(ctx, B_IO + a.slot, a.bytes, &a.dev)) return rc;
+  hipStream_t s = ctx->stream;
+  // on an error path nothing of this call may still be running when the caller's buffers go away
+  auto settled = [&](hipError_t e) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+  };
+  for (const KzgHostArg& a : args)
+    if (a.in) HIP_TRY(ctx, settled(hipMemcpyAsync(a.dev, a.in, a.bytes, hipMemcpyHostToDevice, s)));
+  if (int rc = launch(s)) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  for (const KzgHostArg& a : args)
+    if (a.out) HIP_TRY(ctx, settled(hipMemcpyAsync(a.out, a.dev, a.bytes, hipMemcpyDeviceToHost, s)));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return ECCX_OK;
+}
+}  // namespace
+
+int eccx_kzg_reserve(eccx_ctx* ctx, size_t max_N, size_t max_m) {
+  if (int rc = kzg_args(ctx, max_N, max_m, 0)) return rc;
+  if (max_m == 0) return ECCX_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure_kzg_poly_slab(ctx, max_N, max_m, true, nullptr)) return rc;
+  return eccx_msm_batch_reserve(ctx, ECCX_BLS12_381_G1, max_N, max_m);
+}
+
+int eccx_kzg_eval_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_zs, const void* d_domain, void* d_ys,
+                      void* d_flags, uint32_t opts, void* stream) {
+  return kzg_open_dev(ctx, N, m, d_polys, d_zs, d_domain, nullptr, d_ys, nullptr, d_flags, false, opts, stream);
+}
+int eccx_kzg_eval(eccx_ctx* ctx, size_t N, size_t m, const uint8_t* polys, const uint8_t* zs, const uint8_t* domain, uint8_t* ys,
+                  uint8_t* flags, uint32_t opts) {
+  if (int rc = kzg_args(ctx, N, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, polys && zs && domain && ys && flags)) return rc;
+  KzgHostArg a[] = {{IO_K, polys, nullptr, m * N * 32, nullptr}, {IO_J, zs, nullptr, m * 32, nullptr}, {IO_A, domain, nullptr, N * 32, nullptr},
+                    {IO_O, nullptr, ys, m * 32, nullptr},        {IO_F, nullptr, flags, m, nullptr}};
+  return kzg_host(ctx, a, [&](hipStream_t s) { return eccx_kzg_eval_dev(ctx, N, m, a[0].dev, a[1].dev, a[2].dev, a[3].dev, a[4].dev, opts, s); });
+}
+
+int eccx_kzg_open_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_zs, const void* d_domain, const void* d_srs,
+                      void* d_ys, void* d_proofs, void* d_flags, uint32_t opts, void* stream) {
+  return kzg_open_dev(ctx, N, m, d_polys, d_zs, d_domain, d_srs, d_ys, d_proofs, d_flags, true, opts, stream);
+}
+int eccx_kzg_open(eccx_ctx* ctx, size_t N, size_t m, const uint8_t* polys, const uint8_t* zs, const uint8_t* domain, const uint8_t* srs,
+                  uint8_t* ys, uint8_t* proofs, uint8_t* flags, uint32_t opts) {
+  if (int rc = kzg_args(ctx, N, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, polys && zs && domain && srs && ys && proofs && flags)) return rc;
+  KzgHostArg a[] = {{IO_K, polys, nullptr, m * N * 32, nullptr}, {IO_J, zs, nullptr, m * 32, nullptr},   {IO_A, domain, nullptr, N * 32, nullptr},
+                    {IO_P, srs, nullptr, N * 96, nullptr},       {IO_O, nullptr, ys, m * 32, nullptr},   {IO_B, nullptr, proofs, m * 48, nullptr},
+                    {IO_F, nullptr, flags, m, nullptr}};
+  return kzg_host(ctx, a, [&](hipStream_t s) {
+    return eccx_kzg_open_dev(ctx, N, m, a[0].dev, a[1].dev, a[2].dev, a[3].dev, a[4].dev, a[5].dev, a[6].dev, opts, s);
+  });
+}
+
+int eccx_kzg_commit_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_srs, void* d_commitments, void* d_flags,
+                        uint32_t opts, void* stream) {
+  if (int rc = kzg_args(ctx, N, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_polys && d_srs && d_commitments && d_flags)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  KzgPolySlab b;
+  if (int rc = ensure_kzg_poly_slab(ctx, N, m, false, &b)) return rc;
+  // the range test, the sums over the setup (which take any 256-bit scalar), the compressor, the zeroing of what the test refused
+  HIP_TRY(ctx, eccx::launch_kzg_range(s, N, m, static_cast<const uint8_t*>(d_polys), b.pre));
+  if (int rc = eccx_msm_batch_dev(ctx, ECCX_BLS12_381_G1, N, m, d_polys, d_srs, nullptr, b.sum, b.sum_fl, 0, s)) return rc;
+  if (int rc = eccx_point_compress_dev(ctx, ECCX_BLS12_381_G1, m, b.sum, b.sum_fl, d_commitments, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_kzg_finish(s, m, b.pre, b.sum_fl, static_cast<uint8_t*>(d_commitments), 48, static_cast<uint8_t*>(d_flags)));
+  return ECCX_OK;
+}
+int eccx_kzg_commit(eccx_ctx* ctx, size_t N, size_t m, const uint8_t* polys, const uint8_t* srs, uint8_t* commitments, uint8_t* flags,
+                    uint32_t opts) {
+  if (int rc = kzg_args(ctx, N, m, opts)) return rc;
+  if (m == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, polys && srs && commitments && flags)) return rc;
+  KzgHostArg a[] = {{IO_K, polys, nullptr, m * N * 32, nullptr}, {IO_P, srs, nullptr, N * 96, nullptr},
+                    {IO_B, nullptr, commitments, m * 48, nullptr}, {IO_F, nullptr, flags, m, nullptr}};
+  return kzg_host(ctx, a, [&](hipStream_t s) { return eccx_kzg_commit_dev(ctx, N, m, a[0].dev, a[1].dev, a[2].dev, a[3].dev, opts, s); });
+}
+
+int eccx_kzg_verify_dev(eccx_ctx* ctx, size_t n, const void* d_commitments, const void* d_zs, const void* d_ys, const void* d_proofs,
+                        const uint8_t* tau_g2, void* d_verdicts, uint32_t opts, void* stream) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts) return arg_err(ctx, "eccx_kzg_verify: opts must be 0");
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, d_commitments && d_zs && d_ys && d_proofs && tau_g2 && d_verdicts)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  KzgVerifySlab b;
+  if (int rc = ensure_kzg_verify_slab(ctx, n, &b)) return rc;
+  uint8_t* verdicts = static_cast<uint8_t*>(d_verdicts);
+  // both decoders with their in-place subgroup tests; the identity is a legal commitment and a legal proof
+  if (int rc = eccx_point_decompress_dev(ctx, ECCX_BLS12_381_G1, n, d_commitments, b.c, b.c_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+  if (int rc = eccx_point_decompress_dev(ctx, ECCX_BLS12_381_G1, n, d_proofs, b.p, b.p_fl, ECCX_CHECK_SUBGROUP, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_kzg_verify_prepare(s, n, static_cast<const uint8_t*>(d_zs), static_cast<const uint8_t*>(d_ys), b.c_fl, b.p_fl, b.p,
+                                               b.u1, b.u2, verdicts));
+  // T = [-y]G1 + [z]pi on the fused ladder, A = C + T by the group law, e(A, -G2) e(pi, [tau]G2) == 1 by the pairing check
+  if (int rc = eccx_double_scalarmul_dev(ctx, ECCX_BLS12_381_G1, n, b.u1, b.u2, b.p, b.t, b.t_fl, 0, s)) return rc;
+  if (int rc = eccx_point_add_dev(ctx, ECCX_BLS12_381_G1, n, b.c, b.c_fl, b.t, b.t_fl, b.a, b.a_fl, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_kzg_verify_assemble(s, n, b.a, b.a_fl, b.p, b.p_fl, tau_g2, b.g1, b.g1_inf, b.g2, b.g2_inf, verdicts));
+  if (int rc = pairing_dev(ctx, n, 2, b.g1, b.g1_inf, b.g2, b.g2_inf, nullptr, false, b.pv, 0, s)) return rc;
+  HIP_TRY(ctx, eccx::launch_bls_fold(s, n, b.pv, verdicts));
+  return ECCX_OK;
+}
+int eccx_kzg_verify(eccx_ctx* ctx, size_t n, const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys, const uint8_t* proofs,
+                    const uint8_t* tau_g2, uint8_t* verdicts, uint32_t opts) {
+  if (!ctx) return ECCX_ERR_ARG;
+  if (opts) return arg_err(ctx, "eccx_kzg_verify: opts must be 0");
+  if (n == 0) return ECCX_OK;
+  if (int rc = begin_batch(ctx, commitments && zs && ys && proofs && tau_g2 && verdicts)) return rc;
+  HostBuf bufs[] = {in_buf(IO_K, commitments, 48), in_buf(IO_J, zs, 32), in_buf(IO_A, ys, 32), in_buf(IO_P, proofs, 48), out_buf(IO_F, verdicts, 1)};
+  return host_pipeline(ctx, n, bufs, /*chunked=*/false, [&](size_t, size_t cnt, uint8_t* const* d) {
+    return eccx_kzg_verify_dev(ctx, cnt, d[0], d[1], d[2], d[3], tau_g2, d[4], opts, ctx->stream);
+  });
 }
 
 size_t eccx_pairing_lanes(const eccx_ctx* ctx) {

@@ -324,6 +324,26 @@ hipError_t launch_bls_batch_assemble(hipStream_t s, size_t n, size_t batches, in
                                      const uint8_t* agg, const uint8_t* agg_fl, const uint32_t* pre, uint8_t* g1, uint8_t* g1_inf,
                                      uint8_t* g2, uint8_t* g2_inf, uint64_t* term_offsets, uint8_t* verdicts);
 
+// KZG commitments (kernels_kzg.hpp, k_bls12_381_kzg.hip).  launch_kzg_eval_quotient: m workgroups, one per polynomial of N
+// evaluations (N a power of two): ys[g] = p_g(zs[g]) and, where quot is not null, the m x N quotient evaluations
+// (p_g(X) - y_g) / (X - z_g) as canonical big-endian scalars; flags 0, or 2 with zero bytes where the polynomial, its point or
+// a domain element is not below r.  ninv_be: N^-1 mod r, 32 big-endian bytes on the HOST; ws: kzg_workspace_bytes(N, m).
+// launch_kzg_range is the range test alone; launch_kzg_finish folds it and the sum's flag into 0 / 2 and zeroes a rejected
+// polynomial's `width` bytes of output.  launch_kzg_verify_prepare writes the fused ladder's scalars u1 = -y, u2 = z, puts
+// a finite stand-in where the decoded proof is the identity or the opening is refused, and the verdicts the flags decide;
+// launch_kzg_verify_assemble writes the terms (A, -G2) (proof, [tau]G2) of the pairing check, tau_g2 a 192-byte record on
+// the HOST.
+size_t kzg_workspace_bytes(size_t N, size_t m);
+hipError_t launch_kzg_eval_quotient(hipStream_t s, size_t N, size_t m, const uint8_t* polys, const uint8_t* zs, const uint8_t* domain,
+                                    const uint8_t* ninv_be, uint32_t* ws, uint8_t* ys, uint8_t* quot, uint8_t* flags);
+hipError_t launch_kzg_range(hipStream_t s, size_t N, size_t m, const uint8_t* polys, uint8_t* flags);
+hipError_t launch_kzg_finish(hipStream_t s, size_t m, const uint8_t* pre, const uint8_t* sum_fl, uint8_t* out, int width, uint8_t* flags);
+hipError_t launch_kzg_verify_prepare(hipStream_t s, size_t n, const uint8_t* zs, const uint8_t* ys, const uint8_t* c_fl, const uint8_t* p_fl,
+                                     uint8_t* proof_xy, uint8_t* u1, uint8_t* u2, uint8_t* verdicts);
+hipError_t launch_kzg_verify_assemble(hipStream_t s, size_t n, const uint8_t* a_xy, const uint8_t* a_fl, const uint8_t* proof_xy,
+                                      const uint8_t* p_fl, const uint8_t* tau_g2, uint8_t* g1, uint8_t* g1_inf, uint8_t* g2,
+                                      uint8_t* g2_inf, uint8_t* verdicts);
+
 constexpr int LAUNCH_WG = 256;
 
 template <class K>

@@ -47,6 +47,9 @@ PREP_BLS = 32768
 PREP_PAIRING_GROUPS = 65536
 PREP_BLS_AGGREGATE = 131072
 PREP_BLS_BATCH = 262144
+PREP_KZG = 524288
+# the order of BLS12-381's G1 and G2: the modulus of the scalar field Fr, in which KZG's polynomials live
+BLS_R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_REJECTED = 0, 1, 2
 FLAG_FINITE, FLAG_INFINITY, FLAG_REJECTED = 0, 1, 2
 # ECDSA and Ed25519 verdicts (include/eccx.h: ECCX_SIG_*)
@@ -173,7 +176,7 @@ class Engine:
     def reserve(self, curve, max_n: int, *, var: bool = True, mirror: bool = False, ct: bool = False, host: bool = False,
                 ecdsa: bool = False, ed25519: bool = False, ed25519_sign: bool = False, ecdsa_sign: bool = False,
                 h2c: bool = False, pairing: bool = False, x448: bool = False, msm: bool = False, bls: bool = False,
-                pairing_groups: bool = False, bls_aggregate: bool = False, bls_batch: bool = False):
+                pairing_groups: bool = False, bls_aggregate: bool = False, bls_batch: bool = False, kzg: bool = False):
         """eccx_reserve: size the scratch slab and row buffer for batches of up to max_n units; ct: for the
         secret-scalar (ECCX_CT_SCAN) variable-base ladder; ecdsa: the working slabs of ecdsa_verify; ed25519: those of
         ed25519_verify (curve "ed25519"); ed25519_sign: those of ed25519_sign / ed25519_public_key, with the fixed-base
@@ -186,7 +189,8 @@ class Engine:
         slab and rows of pairing_groups / pairing_check_groups (curve "bls12_381_g2") for every shape with n + terms <=
         max_n; bls_aggregate: the slab of bls_aggregate_verify (curve "bls12_381_g2") and what its parts need, for n + terms
         <= max_n; bls_batch: the slab of bls_batch_verify (curve "bls12_381_g2") and what its parts need, for n + batches <=
-        max_n (with host: the host form's copies, message bytes apart)."""
+        max_n (with host: the host form's copies, message bytes apart); kzg: the slab of kzg_verify (curve "bls12_381_g2") and
+        what its parts need, for max_n openings (the polynomial calls have two sizes: reserve_kzg)."""
         self._check(self._lib.eccx_reserve(self._ctx, curve_id(curve), int(max_n),
                                            (PREP_VAR if var else 0) | (PREP_MIRROR if mirror else 0)
                                            | (PREP_CT if ct else 0) | (PREP_HOST if host else 0)
@@ -197,7 +201,7 @@ class Engine:
                                            | (PREP_MSM if msm else 0) | (PREP_BLS if bls else 0)
                                            | (PREP_PAIRING_GROUPS if pairing_groups else 0)
                                            | (PREP_BLS_AGGREGATE if bls_aggregate else 0)
-                                           | (PREP_BLS_BATCH if bls_batch else 0)))
+                                           | (PREP_BLS_BATCH if bls_batch else 0) | (PREP_KZG if kzg else 0)))
 
     def device_bytes(self) -> int:
         return int(self._lib.eccx_device_bytes(self._ctx))
@@ -1405,6 +1409,159 @@ class Engine:
                                           VALIDATE_POINTS if validate else 0, stream)
         self._check(rc)
         return out, flags
+
+    # ---- KZG commitments for polynomials in evaluation form (eccx_kzg_*) -----------------------------------------
+    @staticmethod
+    def kzg_domain(N: int, bit_reversed: bool = True) -> bytes:
+        """The N-th roots of unity w^0 .. w^(N - 1), w = 7^((r - 1) / N) mod r (c-kzg's primitive root), N x 32 big-endian
+        bytes; bit_reversed: in EIP-4844's order, element i being w^(bit reversal of i).  Python integers: the library
+        reads a domain and never generates one."""
+        N = int(N)
+        if N < 1 or N & (N - 1) or N > 1 << 20:
+            raise ValueError("N must be a power of two, 1 .. 2^20")
+        w = pow(7, (BLS_R - 1) // N, BLS_R)
+        roots, x = [], 1
+        for _ in range(N):
+            roots.append(x)
+            x = x * w % BLS_R
+        if bit_reversed and N > 1:
+            bits = N.bit_length() - 1
+            roots = [roots[int(format(i, f"0{bits}b")[::-1], 2)] for i in range(N)]
+        return b"".join(v.to_bytes(32, "big") for v in roots)
+
+    def reserve_kzg(self, max_N: int, max_m: int):
+        """eccx_kzg_reserve: the slab of kzg_eval / kzg_commit / kzg_open and the workspace of the batched multi-scalar
+        multiplication behind them, for every N <= max_N and m <= max_m."""
+        self._check(self._lib.eccx_kzg_reserve(self._ctx, int(max_N), int(max_m)))
+
+    @staticmethod
+    def _kzg_shape(polys_len: int, N: int, m_bytes: Optional[int]) -> int:
+        if N < 1 or polys_len % (N * 32):
+            raise ValueError("polys must hold m x N x 32 bytes")
+        m = polys_len // (N * 32)
+        if m_bytes is not None and m_bytes != m * 32:
+            raise ValueError("zs must hold one 32-byte point per polynomial")
+        return m
+
+    def kzg_eval(self, polys: bytes, zs: bytes, domain: bytes):
+        """ys[g] = p_g(zs[g]) for m polynomials given as N evaluations over `domain` (N x 32 bytes; polys m x N x 32, zs
+        m x 32, all big-endian and below r).  Returns (ys m x 32, flags m): FLAG_REJECTED with zero bytes where an element
+        of the polynomial or its point is not below r (a domain element not below r rejects all)."""
+        if len(domain) % 32:
+            raise ValueError("domain must hold N x 32 bytes")
+        N = len(domain) // 32
+        m = self._kzg_shape(len(polys), N, len(zs))
+        ys, flags = ctypes.create_string_buffer(max(1, m * 32)), ctypes.create_string_buffer(max(1, m))
+        self._check(self._lib.eccx_kzg_eval(self._ctx, N, m, polys, zs, domain, ys, flags, 0))
+        return ys.raw[: m * 32], flags.raw[:m]
+
+    def kzg_commit(self, polys: bytes, srs: bytes):
+        """commitments[g] = sum_i polys[g][i] * srs[i]: srs the setup in Lagrange form, N affine records of 96 bytes in the
+        domain's order.  Returns (m x 48 bytes in the zcash encoding, flags m)."""
+        if len(srs) % 96:
+            raise ValueError("srs must hold N x 96 bytes")
+        N = len(srs) // 96
+        m = self._kzg_shape(len(polys), N, None)
+        out, flags = ctypes.create_string_buffer(max(1, m * 48)), ctypes.create_string_buffer(max(1, m))
+        self._check(self._lib.eccx_kzg_commit(self._ctx, N, m, polys, srs, out, flags, 0))
+        return out.raw[: m * 48], flags.raw[:m]
+
+    def kzg_open(self, polys: bytes, zs: bytes, domain: bytes, srs: bytes):
+        """EIP-4844's compute_kzg_proof for m polynomials: returns (ys m x 32, proofs m x 48, flags m)."""
+        if len(domain) % 32 or len(srs) != len(domain) * 3:
+            raise ValueError("domain must hold N x 32 bytes and srs N x 96")
+        N = len(domain) // 32
+        m = self._kzg_shape(len(polys), N, len(zs))
+        ys, proofs = ctypes.create_string_buffer(max(1, m * 32)), ctypes.create_string_buffer(max(1, m * 48))
+        flags = ctypes.create_string_buffer(max(1, m))
+        self._check(self._lib.eccx_kzg_open(self._ctx, N, m, polys, zs, domain, srs, ys, proofs, flags, 0))
+        return ys.raw[: m * 32], proofs.raw[: m * 48], flags.raw[:m]
+
+    def _kzg_tau(self, tau_g2: bytes) -> bytes:
+        """[tau]G2 as the 192-byte record the C ABI takes, from that record or from its 96-byte encoding.  The C ABI
+        leaves it to the caller that this is a point of G2: checked here, once per distinct value, by the decoder with its
+        subgroup test (a record goes through the encoder first and must come back as it was)."""
+        tau_g2 = bytes(tau_g2)
+        if len(tau_g2) not in (96, 192):
+            raise ValueError("tau_g2 must be a 96-byte encoding or a 192-byte record of a point of G2")
+        cache = self.__dict__.setdefault("_kzg_tau_cache", {})
+        if tau_g2 not in cache:
+            enc = tau_g2 if len(tau_g2) == 96 else self.point_compress("bls12_381_g2", tau_g2, b"\0")
+            rec, fl = self.point_decompress("bls12_381_g2", enc, check_subgroup=True)
+            if fl != b"\0" or (len(tau_g2) == 192 and rec != tau_g2):
+                raise ValueError("tau_g2 is not a finite point of G2")
+            cache[tau_g2] = rec
+        return cache[tau_g2]
+
+    def kzg_verify(self, commitments: bytes, zs: bytes, ys: bytes, proofs: bytes, tau_g2: bytes) -> bytes:
+        """n independent openings: SIG_MALFORMED where a commitment or proof does not decode or is outside G1 or z or y is
+        not below r, else SIG_VALID iff e(C - [y]G1 + [z]pi, -G2) e(pi, [tau]G2) = 1, else SIG_INVALID.  tau_g2: the
+        96-byte encoding of [tau]G2 (checked once to be in G2) or its 192-byte record (the caller vouches for it)."""
+        if len(zs) % 32:
+            raise ValueError("zs must hold n x 32 bytes")
+        n = len(zs) // 32
+        if len(ys) != n * 32 or len(commitments) != n * 48 or len(proofs) != n * 48:
+            raise ValueError("commitments and proofs hold n x 48 bytes, zs and ys n x 32")
+        v = ctypes.create_string_buffer(max(1, n))
+        self._check(self._lib.eccx_kzg_verify(self._ctx, n, commitments, zs, ys, proofs, self._kzg_tau(tau_g2), v, 0))
+        return v.raw[:n]
+
+    def _kzg_t(self, first, stream):
+        import torch
+
+        return torch.cuda.current_stream(first.device).cuda_stream if stream is None else stream
+
+    def kzg_eval_t(self, polys, zs, domain, ys=None, flags=None, *, stream: Optional[int] = None):
+        """Device-tensor form of kzg_eval (torch.uint8 CUDA tensors): enqueued on the stream, nothing is synchronised."""
+        import torch
+
+        N, m = self._units(domain, 32, "domain"), self._units(zs, 32, "zs")
+        ys = torch.empty((m * 32,), dtype=torch.uint8, device=zs.device) if ys is None else ys
+        flags = torch.empty((m,), dtype=torch.uint8, device=zs.device) if flags is None else flags
+        self._tensors(N, ("domain", domain, 32))
+        self._tensors(m, ("polys", polys, N * 32), ("zs", zs, 32), ("ys", ys, 32), ("flags", flags, 1))
+        self._check(self._lib.eccx_kzg_eval_dev(self._ctx, N, m, polys.data_ptr(), zs.data_ptr(), domain.data_ptr(), ys.data_ptr(),
+                                                flags.data_ptr(), 0, self._kzg_t(zs, stream)))
+        return ys, flags
+
+    def kzg_commit_t(self, polys, srs, commitments=None, flags=None, *, stream: Optional[int] = None):
+        """Device-tensor form of kzg_commit."""
+        import torch
+
+        N = self._units(srs, 96, "srs")
+        m = self._units(polys, max(1, N) * 32, "polys")
+        commitments = torch.empty((m * 48,), dtype=torch.uint8, device=srs.device) if commitments is None else commitments
+        flags = torch.empty((m,), dtype=torch.uint8, device=srs.device) if flags is None else flags
+        self._tensors(N, ("srs", srs, 96))
+        self._tensors(m, ("polys", polys, N * 32), ("commitments", commitments, 48), ("flags", flags, 1))
+        self._check(self._lib.eccx_kzg_commit_dev(self._ctx, N, m, polys.data_ptr(), srs.data_ptr(), commitments.data_ptr(),
+                                                  flags.data_ptr(), 0, self._kzg_t(srs, stream)))
+        return commitments, flags
+
+    def kzg_open_t(self, polys, zs, domain, srs, ys=None, proofs=None, flags=None, *, stream: Optional[int] = None):
+        """Device-tensor form of kzg_open: returns (ys, proofs, flags)."""
+        import torch
+
+        N, m = self._units(domain, 32, "domain"), self._units(zs, 32, "zs")
+        ys = torch.empty((m * 32,), dtype=torch.uint8, device=zs.device) if ys is None else ys
+        proofs = torch.empty((m * 48,), dtype=torch.uint8, device=zs.device) if proofs is None else proofs
+        flags = torch.empty((m,), dtype=torch.uint8, device=zs.device) if flags is None else flags
+        self._tensors(N, ("domain", domain, 32), ("srs", srs, 96))
+        self._tensors(m, ("polys", polys, N * 32), ("zs", zs, 32), ("ys", ys, 32), ("proofs", proofs, 48), ("flags", flags, 1))
+        self._check(self._lib.eccx_kzg_open_dev(self._ctx, N, m, polys.data_ptr(), zs.data_ptr(), domain.data_ptr(), srs.data_ptr(),
+                                                ys.data_ptr(), proofs.data_ptr(), flags.data_ptr(), 0, self._kzg_t(zs, stream)))
+        return ys, proofs, flags
+
+    def kzg_verify_t(self, commitments, zs, ys, proofs, tau_g2: bytes, verdicts=None, *, stream: Optional[int] = None):
+        """Device-tensor form of kzg_verify; tau_g2 stays a host argument, as in kzg_verify."""
+        import torch
+
+        n = self._units(zs, 32, "zs")
+        verdicts = torch.empty((n,), dtype=torch.uint8, device=zs.device) if verdicts is None else verdicts
+        self._tensors(n, ("commitments", commitments, 48), ("zs", zs, 32), ("ys", ys, 32), ("proofs", proofs, 48), ("verdicts", verdicts, 1))
+        self._check(self._lib.eccx_kzg_verify_dev(self._ctx, n, commitments.data_ptr(), zs.data_ptr(), ys.data_ptr(), proofs.data_ptr(),
+                                                  self._kzg_tau(tau_g2), verdicts.data_ptr(), 0, self._kzg_t(zs, stream)))
+        return verdicts
 
     def point_sum_t(self, curve, points, offsets, out=None, flags=None, *, inf=None, validate: bool = False,
                     stream: Optional[int] = None):

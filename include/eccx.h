@@ -294,6 +294,10 @@ enum {
                                    before), and with it what the decoders, the hash, the short multiplications, the sums and
                                    the ragged pairing product need; with ECCX_PREP_HOST the host form's copies of everything
                                    but the message bytes, which no n bounds */
+  ECCX_PREP_KZG = 1u << 19,     /* eccx_reserve (bls12_381_g2): the working slab of eccx_kzg_verify for max_n openings, and with
+                                   it what the fused ladder and the group law on bls12_381_g1 and the pairing (pairs = 2) need
+                                   (the comb table of bls12_381_g1 is eccx_prepare's; the polynomial entry points have two
+                                   sizes and are eccx_kzg_reserve's) */
   ECCX_PREP_CT_GATHER = 1u << 5, /* ECCX_CT_SCAN | ECCX_CT_GATHER: eccx_prepare builds that form's table */
   ECCX_PREP_CT = 1u << 4        /* ECCX_CT_SCAN: eccx_prepare builds the signed-window table of the secret-scalar
                                    fixed-base kernel (99-460 KB); eccx_reserve sizes the slabs of the scanning
@@ -875,6 +879,58 @@ int eccx_bls_batch_verify(eccx_ctx* ctx, size_t n, const uint8_t* msgs, const ui
 int eccx_bls_batch_verify_dev(eccx_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len,
                               const void* d_sigs, const void* d_pubkeys, const void* d_coeffs, size_t batches,
                               const void* d_batch_offsets, void* d_verdicts, void* d_member_status, uint32_t opts, void* stream);
+
+/* KZG polynomial commitments on BLS12-381 (Kate, Zaverucha, Goldberg) for polynomials in EVALUATION form, as EIP-4844 uses
+ * them: commit, evaluate, open at a point, verify an opening.  r is the order of G1.
+ *   N, m     : m polynomials of N evaluations each; N a power of two, 1 <= N <= 2^20, and m x N <= 2^27
+ *   polys    : m x N x 32: polynomial g is its N evaluations over `domain`, 32 big-endian bytes each, canonical (below r)
+ *   domain   : N x 32: N distinct N-th roots of unity, canonical, in the CALLER's order (EIP-4844: bit-reversed).  The library
+ *              reads the domain and never generates it; a domain that is not what this line says gives unspecified values,
+ *              never an out-of-bounds access.
+ *   srs      : N affine x || y records of 96 bytes: the setup's points in LAGRANGE form, [L_i(tau)]G1, in the domain's order
+ *   zs, ys   : m x 32 (n x 32 for eccx_kzg_verify): evaluation points and values, canonical
+ *   flags    : m bytes: 0, or ECCX_FLAG_REJECTED with zero bytes in every output of that polynomial where an element of the
+ *              polynomial or its z is not below r; a domain element not below r rejects all m polynomials (eccx_kzg_eval,
+ *              eccx_kzg_open), as a rejected point of the setup does (eccx_msm_batch's rule).  Neighbours of a rejected
+ *              polynomial stand.
+ * eccx_kzg_eval   ys[g] = p_g(zs[g]) by the barycentric formula, or the evaluation itself where z is in the domain.
+ * eccx_kzg_commit commitments[g] = sum_i polys[g][i] * srs[i], 48 bytes in the zcash encoding; the zero polynomial gives the
+ *                 encoding of the point at infinity.
+ * eccx_kzg_open   EIP-4844's compute_kzg_proof: ys as eccx_kzg_eval, proofs[g] = the commitment to the quotient
+ *                 (p_g(X) - y_g) / (X - z_g), 48 bytes, with the quotient's special case where z is in the domain.  A constant
+ *                 polynomial has the point at infinity as its proof, which eccx_kzg_verify accepts.
+ * eccx_kzg_verify n independent openings (commitments and proofs n x 48, zs and ys n x 32): ECCX_SIG_MALFORMED where the
+ *                 commitment or the proof does not decode or is outside G1, or z or y is not below r; otherwise
+ *                 ECCX_SIG_VALID iff e(C - [y]G1 + [z]pi, -G2) e(pi, [tau]G2) = 1, else ECCX_SIG_INVALID.  ECCX_SIG_BAD_KEY is
+ *                 never returned: the identity is a legal commitment and a legal proof.  tau_g2 is a HOST buffer in both
+ *                 forms, the 192-byte record of [tau]G2, which the CALLER guarantees to be a point of G2
+ *                 (eccx_point_decompress with ECCX_CHECK_SUBGROUP tests one).
+ * opts must be 0: any bit is ECCX_ERR_ARG before anything is launched, as are a null buffer, N == 0 with m > 0, an N that
+ * is no power of two or above 2^20, and m x N above 2^27.  m == 0 (n == 0) returns ECCX_OK.  Every size and launch is a
+ * function of (N, m), or of n, alone and nothing is read back.  The _dev forms enqueue on `stream` and return; after
+ * eccx_kzg_reserve(ctx, max_N, max_m) the polynomial entry points with N <= max_N and m <= max_m, and after
+ * eccx_reserve(ctx, ECCX_BLS12_381_G2, max_n, ECCX_PREP_KZG) eccx_kzg_verify_dev with n <= max_n, neither allocate, free nor
+ * synchronise (eccx_kzg_verify_dev uses the comb table of bls12_381_g1: eccx_prepare builds it ahead of time). */
+int eccx_kzg_eval(eccx_ctx* ctx, size_t N, size_t m, const uint8_t* polys, const uint8_t* zs, const uint8_t* domain, uint8_t* ys,
+                  uint8_t* flags, uint32_t opts);
+int eccx_kzg_eval_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_zs, const void* d_domain, void* d_ys,
+                      void* d_flags, uint32_t opts, void* stream);
+int eccx_kzg_commit(eccx_ctx* ctx, size_t N, size_t m, const uint8_t* polys, const uint8_t* srs, uint8_t* commitments, uint8_t* flags,
+                    uint32_t opts);
+int eccx_kzg_commit_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_srs, void* d_commitments, void* d_flags,
+                        uint32_t opts, void* stream);
+int eccx_kzg_open(eccx_ctx* ctx, size_t N, size_t m, const uint8_t* polys, const uint8_t* zs, const uint8_t* domain, const uint8_t* srs,
+                  uint8_t* ys, uint8_t* proofs, uint8_t* flags, uint32_t opts);
+int eccx_kzg_open_dev(eccx_ctx* ctx, size_t N, size_t m, const void* d_polys, const void* d_zs, const void* d_domain, const void* d_srs,
+                      void* d_ys, void* d_proofs, void* d_flags, uint32_t opts, void* stream);
+int eccx_kzg_verify(eccx_ctx* ctx, size_t n, const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys, const uint8_t* proofs,
+                    const uint8_t* tau_g2, uint8_t* verdicts, uint32_t opts);
+int eccx_kzg_verify_dev(eccx_ctx* ctx, size_t n, const void* d_commitments, const void* d_zs, const void* d_ys, const void* d_proofs,
+                        const uint8_t* tau_g2, void* d_verdicts, uint32_t opts, void* stream);
+/* Sizes the working slab of eccx_kzg_eval_dev, eccx_kzg_commit_dev and eccx_kzg_open_dev and the workspace of the batched
+ * multi-scalar multiplication behind them for every N <= max_N and m <= max_m (the shape rules apply to (max_N, max_m)
+ * itself: ECCX_ERR_ARG): 68 bytes per evaluation, and eccx_msm_batch_reserve's workspace. */
+int eccx_kzg_reserve(eccx_ctx* ctx, size_t max_N, size_t max_m);
 
 /* X25519: the curve25519 x-only Montgomery ladder.
  *   default            protocol::x25519::x25519 (src/protocol/x25519.rs:36-45): `scalars` are

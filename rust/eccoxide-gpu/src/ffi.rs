@@ -70,6 +70,7 @@ pub const ECCX_PREP_MSM: u32 = 1 << 14; // eccx_msm's workspace for every n <= m
 pub const ECCX_PREP_PAIRING_GROUPS: u32 = 1 << 16; // eccx_pairing_groups' slab and rows for n + terms <= max_n (bls12_381_g2)
 pub const ECCX_PREP_BLS_AGGREGATE: u32 = 1 << 17; // eccx_bls_aggregate_verify's slab for n + terms <= max_n (bls12_381_g2)
 pub const ECCX_PREP_BLS_BATCH: u32 = 1 << 18; // eccx_bls_batch_verify's slab for n + batches <= max_n (bls12_381_g2)
+pub const ECCX_PREP_KZG: u32 = 1 << 19; // eccx_kzg_verify's slab for max_n openings (bls12_381_g2)
 
 // per-unit flags
 pub const ECCX_FLAG_FINITE: u8 = 0;
@@ -262,6 +263,33 @@ extern "C" {
                                      dst_len: usize, d_sigs: *const c_void, d_pubkeys: *const c_void, d_coeffs: *const c_void,
                                      batches: usize, d_batch_offsets: *const c_void, d_verdicts: *mut c_void,
                                      d_member_status: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    // KZG commitments for polynomials in evaluation form: m polynomials of N evaluations over the caller's domain
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_eval(ctx: *mut eccx_ctx, N: usize, m: usize, polys: *const u8, zs: *const u8, domain: *const u8, ys: *mut u8,
+                         flags: *mut u8, opts: u32) -> c_int;
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_eval_dev(ctx: *mut eccx_ctx, N: usize, m: usize, d_polys: *const c_void, d_zs: *const c_void, d_domain: *const c_void,
+                             d_ys: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_commit(ctx: *mut eccx_ctx, N: usize, m: usize, polys: *const u8, srs: *const u8, commitments: *mut u8, flags: *mut u8,
+                           opts: u32) -> c_int;
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_commit_dev(ctx: *mut eccx_ctx, N: usize, m: usize, d_polys: *const c_void, d_srs: *const c_void,
+                               d_commitments: *mut c_void, d_flags: *mut c_void, opts: u32, stream: *mut c_void) -> c_int;
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_open(ctx: *mut eccx_ctx, N: usize, m: usize, polys: *const u8, zs: *const u8, domain: *const u8, srs: *const u8,
+                         ys: *mut u8, proofs: *mut u8, flags: *mut u8, opts: u32) -> c_int;
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_open_dev(ctx: *mut eccx_ctx, N: usize, m: usize, d_polys: *const c_void, d_zs: *const c_void, d_domain: *const c_void,
+                             d_srs: *const c_void, d_ys: *mut c_void, d_proofs: *mut c_void, d_flags: *mut c_void, opts: u32,
+                             stream: *mut c_void) -> c_int;
+    pub fn eccx_kzg_verify(ctx: *mut eccx_ctx, n: usize, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8,
+                           tau_g2: *const u8, verdicts: *mut u8, opts: u32) -> c_int;
+    pub fn eccx_kzg_verify_dev(ctx: *mut eccx_ctx, n: usize, d_commitments: *const c_void, d_zs: *const c_void, d_ys: *const c_void,
+                               d_proofs: *const c_void, tau_g2: *const u8, d_verdicts: *mut c_void, opts: u32,
+                               stream: *mut c_void) -> c_int;
+    #[allow(non_snake_case)]
+    pub fn eccx_kzg_reserve(ctx: *mut eccx_ctx, max_N: usize, max_m: usize) -> c_int;
     pub fn eccx_bls_fast_aggregate_verify(ctx: *mut eccx_ctx, n: usize, msgs: *const u8, offsets: *const u64, dst: *const u8,
                                           dst_len: usize, sigs: *const u8, pubkeys: *const u8, key_offsets: *const u64, keys: usize,
                                           verdicts: *mut u8, opts: u32) -> c_int;
